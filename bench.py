@@ -16,11 +16,19 @@ Other workloads (`--workload`): config2 (XGBoost only on HBM-resident vectors), 
 GPU, no routing), config5 (+ LSTM head, 1k latency batches), ingest (JSON codec), config3j (config3 from
 raw JSON).
 
-Reported beside the throughput: p50/p99 micro-batch latency (host submit -> scores in host memory), the
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure needs: setup, W warm-up
+steps, the N timed steps, and one JSON result line (metric, value, unit, higher_is_better, dtype, ms_per_step,
+the workload's configuration). `--dump-outputs DIR` also writes what the last timed step computed — the arrays
+its caller receives — as DIR/<name>.npy (float32 / float64; the inputs are seeded, so two builds run with the
+same arguments can be compared output for output).
+
+`--full` adds everything else, reported beside the throughput: the parity spot-check against the CPU oracle (run
+before the warm-up, as it always was), p50/p99 micro-batch latency (host submit -> scores in host memory), the
 dominant kernel's roofline against ITS bound (the forest walk: LDS issue, node-steps/s against the
 LDS-array ceiling), the fused pipeline's algorithmic HBM bytes (SURVEY §8(d), 238 B/txn), per-kernel
-times, and the CPU baseline: the oracle C restatement of the whole chain on a config-1-shaped stream
-(100k simulator transactions), at 1 core and at the host threads available (rank 0, N=1 only).
+times, the other BASELINE configurations as child processes (config 4, N=1), and the CPU baseline: the oracle C
+restatement of the whole chain on a config-1-shaped stream (100k simulator transactions), at 1 core and at the
+host threads available (rank 0, N=1 only).
 """
 import argparse
 import gc
@@ -318,6 +326,48 @@ def hip_d2h(dst: int, src: int, nbytes: int, stream: int) -> None:
     hip_memcpy_async(dst, src, nbytes, 2, stream)
 
 
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs: all files of one rank together (under 64 MB with the .npy headers)
+
+
+def _float_columns(named) -> dict:
+    """{name: device tensor or host array} -> {name: float32 / float64 host array}, values kept exactly: floats as
+    they are, integers of up to 4 bytes as float64, 8-byte integers (card keys, hashes, timestamps) as two float64
+    columns <name>_lo / <name>_hi of their 32-bit halves."""
+    import numpy as np
+    out = {}
+    for name, a in named.items():
+        a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
+        if a.dtype in (np.float32, np.float64):
+            out[name] = a
+        elif a.dtype.itemsize == 8:
+            u = a.view(np.uint64)
+            out[name + "_lo"] = (u & np.uint64(0xFFFFFFFF)).astype(np.float64)
+            out[name + "_hi"] = (u >> np.uint64(32)).astype(np.float64)
+        else:
+            out[name] = a.astype(np.float64)
+    return out
+
+
+def dump_outputs(path, named, rank=0) -> dict:
+    """--dump-outputs: the last timed step's outputs as path/<name>.npy (ranks above 0: <name>.rank<r>.npy). Past
+    DUMP_LIMIT_BYTES in all, the same seeded sample of rows (sorted) of every array is written instead."""
+    import numpy as np
+    cols = _float_columns(named)
+    total = sum(a.nbytes for a in cols.values())
+    rows = min(len(a) for a in cols.values())
+    sampled = None
+    if total > DUMP_LIMIT_BYTES:
+        sampled = max(1, int(rows * (DUMP_LIMIT_BYTES / total)))
+        keep = np.sort(np.random.default_rng(0).choice(rows, sampled, replace=False))
+        cols = {k: a[keep] for k, a in cols.items()}
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, a in cols.items():
+        np.save(d / (f"{k}.npy" if rank == 0 else f"{k}.rank{rank}.npy"), a)
+    return {"dir": str(d), "arrays": {k: [str(a.dtype), list(a.shape)] for k, a in cols.items()},
+            "bytes": int(sum(a.nbytes for a in cols.values())), "sampled_rows": sampled}
+
+
 class PackedColumns:
     """A micro-batch's input columns packed into one buffer (256-B aligned column offsets), so a host batch
     crosses PCIe in ONE hipMemcpyAsync: `host` pinned blocks (one per batch) and two device staging blocks with
@@ -493,6 +543,11 @@ class Config2:
         src = self.prob[s * self.B:(s + 1) * self.B]
         hip_d2h(self.host_out.data_ptr(), src.data_ptr(), src.numel() * 8, self.torch.cuda.current_stream().cuda_stream)
 
+    def last_outputs(self, i):
+        """what step i's caller receives (--dump-outputs): the micro-batch's probabilities"""
+        s = i % self.pool
+        return {"fraud_prob": self.prob[s * self.B:(s + 1) * self.B]}
+
     def parity(self):
         import oracle
         np = self.np
@@ -650,6 +705,10 @@ class Config3:
 
     def outputs(self):
         return self.outs[self.cur] if self.pipe else (self.fp, self.conf, self.dec, self.risk)
+
+    def last_outputs(self, i):
+        """what the last step's caller receives (--dump-outputs)"""
+        return dict(zip(("fraud_prob", "confidence", "decision", "risk"), self.outputs()))
 
     def _parity(self):
         import oracle
@@ -856,7 +915,8 @@ class Config4(Config3):
                     dist.all_gather(parts, k)
                     return torch.cat(parts)
             w = synth_gpu.warm_workload(eng, dev, self.cards, rank, self.world, self.n_batches, B, hours=self.hours,
-                                        keep_batches=self.parity_batches + 1, host_batches=h2d_batches, log=log,
+                                        keep_batches=self.parity_batches + 1 if args.full else 0,
+                                        host_batches=h2d_batches, log=log,
                                         gather_keys=gather)
             self.dev = w["resident"]
             self.tx = w["head"]  # host copies of the parity batches
@@ -935,6 +995,9 @@ class Config4(Config3):
         if "out" not in kw and self.out_sets is not None:
             kw["out"] = self.out_sets[b & 1]
         self.out = self.scorer.step(part, B, **kw)
+
+    def outputs(self):
+        return self.out
 
     def step_to_host(self, i, q):
         """one step whose outputs land in host-mapped pinned memory (HostOutRing set q): no separate D2H"""
@@ -1173,6 +1236,10 @@ class Ingest:
         d = self.cols["status"]
         hip_d2h(self.h_status.data_ptr(), d.data_ptr(), d.numel() * d.element_size(),
                 self.torch.cuda.current_stream().cuda_stream)
+
+    def last_outputs(self, i):
+        """what the last step's caller receives (--dump-outputs): the parsed columns in their own dtypes"""
+        return {name: self.cols[name].cpu().numpy().view(dt) for name, dt in self.N.INGEST_FIELDS}
 
     def parity(self):
         from oracle import ingest_ref as R
@@ -1513,6 +1580,13 @@ def make_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: parity against the CPU oracle, latency loops, kernel timing and "
+                         "roofline, the CPU baseline and (config 4, N = 1) the secondary workloads; without it a run "
+                         "sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB: past that a seeded sample of rows)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="config4")
     ap.add_argument("--batch", type=int, default=None, help="micro-batch per GPU (default 64k; config5: 1k)")
     ap.add_argument("--trees", type=int, default=500)
@@ -1531,7 +1605,7 @@ def make_parser():
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--secondary", default=None,
-                    help="config 4 at N = 1: other BASELINE configurations run after the line's own measurements, each "
+                    help="--full, config 4, N = 1: other BASELINE configurations run after the line's own measurements, each "
                          "as a child process (its own engine, 200 steps), their results embedded as "
                          "secondary_workloads (comma list; default config5,config2,config3,config3j; 'none' or "
                          "FD_BENCH_SECONDARY=0 to skip)")
@@ -1573,6 +1647,10 @@ def parse_args(argv=None):
         args.batch = 1024 if args.workload == "config5" else 65536
     if args.cards is None:
         args.cards = 100_000_000 if args.workload == "config4" else 10_000_000
+    if not args.full:  # the measurements beside the headline belong to --full: none of their batches or loops
+        args.latency_iters = args.alone_iters = args.parity_batches = args.loaded_iters = args.timing_steps = 0
+        args.no_cpu_baseline = True
+        args.secondary = "none"
     return args
 
 
@@ -1618,10 +1696,11 @@ def main():
         eng.set_option("small_streams", args.small_streams)
 
     parity = None
-    try:
-        parity = wl.parity()
-    except Exception as e:  # the oracle is only a checker; report, never fall back
-        log(f"[rank {rank}] parity spot-check unavailable: {e!r}")
+    if args.full:
+        try:
+            parity = wl.parity()
+        except Exception as e:  # the oracle is only a checker; report, never fall back
+            log(f"[rank {rank}] parity spot-check unavailable: {e!r}")
 
     if _diag_offset() and hasattr(wl, "next_batch"):
         wl.next_batch += _diag_offset()
@@ -1735,6 +1814,9 @@ def main():
         dist.barrier()
     t1 = time.perf_counter()
     host1 = _host_counters(eng)
+    dumped = None
+    if args.dump_outputs:  # the last timed step's outputs, before any later step reuses their buffers
+        dumped = dump_outputs(args.dump_outputs, wl.last_outputs(args.steps - 1), rank)
     _dump_fprof(0)
     # diagnostics (FD_BENCH_BLOCKS=N): N more blocks of --steps steps after the timed region, each bracketed by a
     # synchronize, their ms per step in the line (is a short region's rate a first-block effect or its fill / drain?)
@@ -1750,17 +1832,19 @@ def main():
     # kernel durations: HIP events on the launch stream, on one launch in TIMING_EVERY of each kernel (an event
     # record costs stream time), over more of the same back-to-back steps AFTER the timed region, so the kernel
     # averages rest on >= 20 launches of each kernel and `value` carries no instrumentation
-    for e in _engines(eng, wl):
-        e.set_option("timing_every", TIMING_EVERY)
-        e.set_timing(True)
-    for i in range(args.timing_steps):
-        wl.step(args.steps + i)
-    torch.cuda.synchronize()
-    if dist:
-        dist.barrier()
-    for e in _engines(eng, wl):
-        e.set_timing(False)
-    timing = _read_timing(eng, wl)
+    timing = {}
+    if args.full:
+        for e in _engines(eng, wl):
+            e.set_option("timing_every", TIMING_EVERY)
+            e.set_timing(True)
+        for i in range(args.timing_steps):
+            wl.step(args.steps + i)
+        torch.cuda.synchronize()
+        if dist:
+            dist.barrier()
+        for e in _engines(eng, wl):
+            e.set_timing(False)
+        timing = _read_timing(eng, wl)
     elapsed = t1 - t0
     saturation = None
     if sat0 is not None:
@@ -1777,6 +1861,43 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if DIST_BACKEND == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    value = world * args.steps * args.batch / elapsed
+    # the headline: every run's result line starts from these fields
+    headline = {
+        "metric": "scored transactions/sec (whole node)",
+        "value": round(value, 1),
+        "unit": "txn/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+        "host_submit_ms_per_step": round((t_sub - t0) / args.steps * 1e3, 5),
+        "host_submit_breakdown": _host_breakdown(host0, host1, t_sub - t0, args.steps),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": wl.dtype,
+        "data": "synthetic (seeded simulator-distribution stream / scoring vectors; random-init models in the "
+                "reference's file formats)",
+        "full": bool(args.full),
+        "outputs_dumped": dumped,
+        "window_saturation": saturation,
+        "step_launch": "direct kernel launches",
+        "engine_options": dict(kv.split("=") for kv in args.engine_option) or None,
+    }
+    if not args.full:
+        if rank == 0:
+            headline["config"] = dict(wl.config(world), **(
+                {"dist_backend": "gloo rehearsal (ranks share GPUs; not the metric)"}
+                if world > 1 and DIST_BACKEND != "nccl" else {}))
+            if blocks:
+                headline["diag_blocks_ms_per_step"] = blocks
+            print(json.dumps(headline), flush=True)
+        eng.close()
+        if dist:
+            dist.destroy_process_group()
+        return
 
     # loaded latency: the stream at the throughput operating point with a consumer's backpressure — at most
     # --loaded-inflight micro-batches submitted and not yet back (the host waits for batch i-D's results before it
@@ -1854,7 +1975,6 @@ def main():
             e.set_timing(False)
         timing_alone = _read_timing(eng, wl)
 
-    value = world * args.steps * args.batch / elapsed
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = wl.cpu_baseline(args.cpu_seconds)
@@ -1877,22 +1997,8 @@ def main():
                                  "every launch timed (no other kernel on the CUs)"}
             except Exception as e:  # a workload whose roofline needs the timed region's kernels
                 log(f"[rank {rank}] roofline.alone unavailable: {e!r}")
-        line = {
-            "metric": "scored transactions/sec (whole node)",
-            "value": round(value, 1),
-            "unit": "txn/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-            "host_submit_ms_per_step": round((t_sub - t0) / args.steps * 1e3, 5),
-            "host_submit_breakdown": _host_breakdown(host0, host1, t_sub - t0, args.steps),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": wl.dtype,
-            "data": "synthetic (seeded simulator-distribution stream / scoring vectors; random-init models in the "
-                    "reference's file formats)",
+        line = dict(headline)
+        line.update({
             "config": dict(wl.config(world), **({"dist_backend": "gloo rehearsal (ranks share GPUs; not the metric)"}
                                                if world > 1 and DIST_BACKEND != "nccl" else {})),
             "p50_batch_latency_ms": round(float(np.percentile(lat_ms, 50)), 4),
@@ -1914,10 +2020,7 @@ def main():
                              f"{args.timing_steps} back-to-back steps after the timed region (none inside it)",
             "cpu_baseline": cpu,
             "parity_vs_oracle": parity,
-            "window_saturation": saturation,
-            "step_launch": "direct kernel launches",
-            "engine_options": dict(kv.split("=") for kv in args.engine_option) or None,
-        }
+        })
         if blocks:
             line["diag_blocks_ms_per_step"] = blocks
         if hasattr(wl, "counter_groups"):
@@ -1960,13 +2063,13 @@ def _secondary_list(args, world, name):
 
 
 def _run_secondaries(names):
-    """Each secondary workload as `python bench.py --workload W --steps 200 --warmup 20 --no-cpu-baseline` in a child
-    process (started after this process freed its GPU state; never an exec), its JSON line parsed and summarised:
+    """Each secondary workload as `python bench.py --full --workload W --steps 200 --warmup 20 --no-cpu-baseline` in a
+    child process (started after this process freed its GPU state; never an exec), its JSON line parsed and summarised:
     the other BASELINE configurations measured by the same command the driver runs."""
     out = {}
     for w in names:
-        cmd = [sys.executable, str(Path(__file__).resolve()), "--workload", w, "--steps", "200", "--warmup", "20",
-               "--no-cpu-baseline", "--secondary", "none"]
+        cmd = [sys.executable, str(Path(__file__).resolve()), "--full", "--workload", w, "--steps", "200",
+               "--warmup", "20", "--no-cpu-baseline", "--secondary", "none"]
         a = time.perf_counter()
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)

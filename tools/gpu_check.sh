@@ -29,15 +29,15 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   run pytest_gpu 1100 python -u -m pytest ${TESTS:-tests} -m gpu -x -v --timeout 200 --timeout-method thread \
       -p no:cacheprovider ${PYTEST_K:+-k "$PYTEST_K"}; rc=$?; fatal $rc && exit $rc
 fi
-run bench 900 python bench.py --steps "$STEPS" --warmup 20; rc=$?; fatal $rc && exit $rc
+run bench 900 python bench.py --full --steps "$STEPS" --warmup 20; rc=$?; fatal $rc && exit $rc
 grep '^{' "$OUT/$TAG.bench.log" > "$OUT/$TAG.bench.json" || true
 for wl in ${WORKLOADS:-}; do
-  run "bench_$wl" 600 python bench.py --workload "$wl" --steps "$STEPS" --warmup 20; rc=$?; fatal $rc && exit $rc
+  run "bench_$wl" 600 python bench.py --full --workload "$wl" --steps "$STEPS" --warmup 20; rc=$?; fatal $rc && exit $rc
   grep '^{' "$OUT/$TAG.bench_$wl.log" > "$OUT/$TAG.$wl.bench.json" || true
 done
 if [ "${PROFILE:-1}" = "1" ]; then
   FD_BENCH_SECONDARY=0 run rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$TAG.prof" -o run -- \
-      python "$ROOT/bench.py" --steps 50 --warmup 5 --no-cpu-baseline --latency-iters 10; rc=$?
+      python "$ROOT/bench.py" --full --steps 50 --warmup 5 --no-cpu-baseline --latency-iters 10; rc=$?
   fatal $rc && exit $rc
 fi
 echo "=== done"

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 TAG=${1:-pmc}
 shift
 ARGS=("$@")
-[ ${#ARGS[@]} -eq 0 ] && ARGS=(--workload config3 --steps 10 --warmup 3 --no-cpu-baseline --latency-iters 2)
+[ ${#ARGS[@]} -eq 0 ] && ARGS=(--full --workload config3 --steps 10 --warmup 3 --no-cpu-baseline --latency-iters 2)
 
 PASSES=(
   "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS"

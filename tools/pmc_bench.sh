@@ -8,7 +8,7 @@ i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
   timeout -s KILL 240 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d gpurun_out/$TAG.$WL.p$i -o run -- \
-     python bench.py --workload $WL --steps 20 --warmup 3 --latency-iters 0 --no-cpu-baseline $EXTRA \
+     python bench.py --full --workload $WL --steps 20 --warmup 3 --latency-iters 0 --no-cpu-baseline $EXTRA \
      > gpurun_out/$TAG.$WL.p$i.log 2>&1
   rc=$?; echo "pass $i ($grp) rc=$rc"
   [ $rc -ne 0 ] && exit $rc
