@@ -164,10 +164,11 @@ def test_sampled_kernel_timing(engine):
 
 @pytest.mark.parametrize("kind,depth", [("xgb", 8), ("xgb", 6), ("if", 8)])
 def test_single_forest_fused_equals_kernel6(engine, kind, depth):
-    """fd_forest_predict on a large batch without raw / leaf outputs runs the fused kernel over the one forest
+    """fd_forest_predict on a large batch without leaf outputs runs the fused kernel over the one forest
     (_predict_xgboost / _predict_sklearn, ml/models/model_manager.py:309-311, 338-346): probabilities
     bit-identical to forest kernel 6 (engine option ensemble = 0), NaNs and short rows included; and with raw
-    margins requested the call keeps kernel 6."""
+    scores requested the call still takes the fused kernel (counter ensemble_single_launches; XGBoost margins and
+    IsolationForest depth sums alike), its raw output bit-identical to kernel 6's."""
     nf = 64
     xgb, ifm = _models(nf, depth, n_trees=150, n_if=50, seed=11 + depth)
     model = xgb if kind == "xgb" else ifm
@@ -184,7 +185,9 @@ def test_single_forest_fused_equals_kernel6(engine, kind, depth):
         engine.set_option("ensemble", 1)
     np.testing.assert_array_equal(fused, k6)
     np.testing.assert_array_equal(fused, k6b)
-    _, raw1 = engine.predict(2, X, want_raw=True)  # raw requested: kernel 6 even with the option on
+    c0 = engine.counter("ensemble_single_launches")
+    _, raw1 = engine.predict(2, X, want_raw=True)  # raw requested: still the fused single-forest kernel
+    assert engine.counter("ensemble_single_launches") - c0 == 1
     np.testing.assert_array_equal(raw1, raw)
     short = np.ascontiguousarray(X[:, :48])  # rows shorter than num_feature: missing columns
     np.testing.assert_array_equal(engine.predict(2, short), _k6(engine, 2, short))
