@@ -8,20 +8,28 @@
 // 2^D node records {f32 thr, u32 meta} (slot 0 unused) followed by 2^D leaf values (f32 XGBoost,
 // f64 IsolationForest). meta = feature*1024 (byte offset of the feature's row in the LDS feature
 // tile) | default_left << 31. Trees are grouped in chunks of CH trees (1 KiB-aligned stride) that
-// are staged into LDS by LDS-DMA.
+// are staged into LDS by LDS-DMA. Binned layout (forests whose features have <= 65534 distinct
+// thresholds each): the same heap with ONE u32 word per node (walk_common.h) and bin words in the
+// feature tile; its node-only variant keeps the leaf values out of the chunks, in a [tree][2^D] array.
 //
-// forest_kernel3 (depth <= 8, the configurations on the path): 1024-thread workgroup per tile of 256
-// transactions. The feature tile lives in LDS as [f][256] f32, so a lane reading ANY feature hits
-// bank (lane mod 32): feature gathers are conflict-free. Wave w walks, for the 64 transactions of
-// txn group w&3, TPG = CH/4 trees of each staged chunk. Each level issues the feature read of the
-// selected node AND the 16 B read of its two children together (speculative children): one LDS
-// round trip per level instead of two. Leaf values go to LDS and a rotating owner tree-group adds a
-// chunk's CH values per transaction in tree order, so the sum is the reference's sequential order:
-// XGBoost's f32 margin and sklearn's f64 path-length sum are reproduced bit for bit.
+// Tile kernels (depth <= 8), ONE body (forest_tile_body.h) over three layouts: forest_kernel3 =
+// threshold (forests that cannot be binned), forest_kernel4 = binned (forests with no node-only
+// chunk size, e.g. 64 features with f64 leaves), forest_kernel6 = binned node-only (every other
+// binned forest). 1024-thread workgroup per tile of 256 transactions. The feature tile lives in LDS
+// as [f][256] words, so a lane reading ANY feature hits bank (lane mod 32): feature gathers are
+// conflict-free. Wave w walks, for the 64 transactions of txn group w&3, TPG = CH/4 trees of each
+// staged chunk. Each level issues the feature read of the selected node AND the read of its two
+// children together (speculative children): one LDS round trip per level instead of two. Leaf
+// values go to LDS and a rotating owner tree-group adds a chunk's CH values per transaction in tree
+// order, so the sum is the reference's sequential order: XGBoost's f32 margin and sklearn's f64
+// path-length sum are reproduced bit for bit.
 // forest_kernel1: 256 threads, thread per transaction (deep trees D = 9..10; A/B reference).
+// Small batches: the tree-split path (split_bin / split_walk / split_sum kernels, below).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
+#include <utility>
 
 #include "blend_row.h"
 #include "fd_internal.h"
@@ -69,26 +77,22 @@ size_t round1k(size_t b) { return (b + 1023) / 1024 * 1024; }
 
 }  // namespace
 
-size_t lds_bytes_kernel3(int nf, size_t chunk_stride, int ch, size_t leaf_sz) {
+// LDS image of the tile kernels 3, 4 and 6 (one map for the three layouts: the tile holds f32 values or u32 bin words)
+size_t lds_bytes_tile(int nf, size_t chunk_stride, int ch, size_t leaf_sz) {
   // Xs + 2 chunk buffers + 2 leaf-value buffers + accumulator + 16 wave flags + 1 KiB alignment slack
   return (size_t)nf * kTile * 4 + 2 * chunk_stride + 2 * (size_t)ch * kTile * leaf_sz + kTile * leaf_sz + 64 + 1024;
 }
 
 size_t lds_bytes_kernel1(int nf, size_t chunk_stride) { return (size_t)nf * kTile * 4 + 2 * chunk_stride + 64; }
 
-// forest_kernel4 has kernel 3's LDS map (bins are u32 words, nodes 4 B)
-size_t lds_bytes_kernel4(int nf, size_t chunk_stride, int ch, size_t leaf_sz) {
-  return lds_bytes_kernel3(nf, chunk_stride, ch, leaf_sz);
-}
-
 namespace {
 
 // Trees per staged chunk: for depth <= 8 the largest multiple of 4 (one tree per wave of each of the
-// four tree groups, x TPG) whose LDS image fits forest_kernel3/4's 160 KiB; deeper trees: kernel 1.
+// four tree groups, x TPG) whose LDS image fits the tile kernels' 160 KiB; deeper trees: kernel 1.
 int choose_chunk(int D, int nf, size_t tree_bytes, size_t leaf_sz) {
   if (D <= 8) {
     for (int ch = 16; ch >= 4; ch -= 4)
-      if (lds_bytes_kernel3(nf, round1k(ch * tree_bytes), ch, leaf_sz) <= kLdsBudget) return ch;
+      if (lds_bytes_tile(nf, round1k(ch * tree_bytes), ch, leaf_sz) <= kLdsBudget) return ch;
   }
   for (int ch = 8; ch >= 1; ch /= 2)
     if (lds_bytes_kernel1(nf, round1k(ch * tree_bytes)) <= kLdsBudget) return ch;
@@ -152,7 +156,7 @@ HostPack pack_forest_host(const fd_forest_params& p, const fd_tree_arrays& t, in
   int BCH = 0;
   if (binnable && D <= 8)
     for (int ch = 16; ch >= 4 && !BCH; ch -= 4)
-      if (lds_bytes_kernel4(nf, round1k(ch * b_tree_bytes), ch, leaf_sz) <= kLdsBudget) BCH = ch;
+      if (lds_bytes_tile(nf, round1k(ch * b_tree_bytes), ch, leaf_sz) <= kLdsBudget) BCH = ch;
   binnable = binnable && BCH > 0;
   if (binnable) {
     hp.binned = true;
@@ -231,7 +235,7 @@ HostPack pack_forest_host(const fd_forest_params& p, const fd_tree_arrays& t, in
   }
   if (binnable) {  // node-only chunks for forest_kernel6: the largest supported CH whose LDS image fits
     for (int ch : {32, 24, 16})
-      if (lds_bytes_kernel3(nf, round1k((size_t)ch * NL * 4), ch, leaf_sz) <= kLdsBudget) {
+      if (lds_bytes_tile(nf, round1k((size_t)ch * NL * 4), ch, leaf_sz) <= kLdsBudget) {
         hp.n_chunk = ch;
         break;
       }
@@ -400,16 +404,24 @@ forest_kernel1(const float* __restrict__ X, int64_t n, int ld, int nf, const cha
 }
 
 // ------------------------------------------------------------------------------------------------
-// forest_kernel3 (depth <= 8): 1024 threads on a 256-transaction tile, speculative children.
+// Tile kernels 3, 4 and 6 (depth <= 8): ONE body, forest_tile_body.h, over three chunk layouts. 1024
+// threads on a 256-transaction tile; see the header comment for the schedule.
 //
-// LDS (absolute byte addresses; the kernel has no static LDS, the base is 1 KiB aligned):
-//   [0, nf*1024)      Xs[f][256] f32     x address = (meta & 0x7fffffff) | txn*4 (one v_and_or)
+// LDS (absolute byte addresses; the kernels have no static LDS, the base is 1 KiB aligned):
+//   [0, nf*1024)      Xs[f][256]         f32 values, x address = (meta & 0x7fffffff) | txn*4 (one
+//                                        v_and_or); binned layouts: u32 bin words
 //   bufA, bufB        2 x chunk_stride   staged trees (LDS-DMA, one chunk ahead)
 //   lvA, lvB          2 x [CH][256]      leaf values of the chunk being summed / being walked
 //   accL              [256]              running sum per transaction (LeafT)
 //   flags             16 words           tile_any
 
 constexpr int kWG3 = 1024;
+
+enum class Layout {
+  kThreshold,  // kernel 3: 8-byte nodes {f32 thr, u32 meta}, raw f32 feature tile, leaves in the chunk
+  kBinned,     // kernel 4: 4-byte binned nodes, bin-word feature tile, leaves in the chunk
+  kNodeOnly,   // kernel 6: 4-byte binned nodes ONLY in the chunk, leaves in a global [tree][2^D] array
+};
 
 #ifdef FD_FOREST_PROFILE
 // Phase-cycle instrumentation (s_memtime), built only into the profiling variant of the library:
@@ -429,9 +441,10 @@ __device__ __forceinline__ void opaque4(uint32_t& a, uint32_t& b, uint32_t& c, u
   asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
 }
 
-// Walks TPG trees of the staged chunk at `buf` for this lane's transaction. A[j] is the LDS address
-// of the children pair of the current node (heap slot i: tb + 16 i); per level one feature read and
-// one 16 B read of the chosen child's own children are in flight together. Returns leaf slots.
+// Threshold-layout walk: TPG trees of the staged chunk at `buf` for this lane's transaction. A[j] is
+// the LDS address of the children pair of the current node (heap slot i: tb + 16 i); per level one
+// feature read and one 16 B read of the chosen child's own children are in flight together. Returns
+// leaf slots. (The binned walk, walk4, is in walk_common.h: the fused ensemble kernel shares it.)
 template <int D, int TPG, typename LeafT, bool NAN_AWARE>
 __device__ __forceinline__ void walk3(uint32_t buf, int gg, uint32_t lane4, uint32_t (&slot)[TPG]) {
   constexpr uint32_t TB = (8u + (uint32_t)sizeof(LeafT)) << D;
@@ -484,135 +497,22 @@ __device__ __forceinline__ void walk3(uint32_t buf, int gg, uint32_t lane4, uint
   for (int j = 0; j < TPG; ++j) slot[j] = ((A[j] - tb[j]) >> 4) - NL;  // leaf heap slot - 2^D
 }
 
+// The three kernels: each sets its layout and has the shared body, forest_tile_body.h, as its own text.
+// (The body as a __forceinline__ function template compiled to slightly different code than the kernels it
+// replaced: it is optimised on its own before it is inlined. Included, each kernel compiles as if written out.)
+// thr / thr_off are read by the binned layouts only, leaves by kNodeOnly only.
 template <int D, int CH, typename LeafT, int KIND>
 __global__ void __launch_bounds__(kWG3)
 forest_kernel3(const float* __restrict__ X, int64_t n, int ld, int nf, const char* __restrict__ blob,
                int n_chunks, int chunk_stride, const int32_t* __restrict__ leaf_ids, int n_trees,
                float base_margin, double if_offset, double if_denom, double* __restrict__ out_prob,
                double* __restrict__ out_raw, int32_t* __restrict__ out_leaf) {
-  constexpr int TPG = CH / 4;
-  constexpr int NL = 1 << D;
-  constexpr uint32_t TB = (8u + (uint32_t)sizeof(LeafT)) << D;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  // 1 KiB-aligned base: no static LDS in this kernel (so the base is 0); 1 KiB slack reserved anyway
-  const uint32_t sdyn = (uint32_t)(size_t)((lds_char*)smem);
-  const uint32_t s0 = (sdyn + 1023u) & ~1023u;
-  char* const lbase = smem + (s0 - sdyn);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int gg = wave >> 2;                  // tree group
-  const int txn = ((wave & 3) << 6) + lane;  // 0..255 within the tile
-  const uint32_t lane4 = s0 + (uint32_t)txn * 4u;
-  const uint32_t xbytes = (uint32_t)nf * 1024u;
-  const uint32_t bufA = s0 + xbytes, bufB = bufA + (uint32_t)chunk_stride;
-  const uint32_t lvA = bufB + (uint32_t)chunk_stride;
-  const uint32_t lvB = lvA + CH * kTile * sizeof(LeafT);
-  const uint32_t accL = lvB + CH * kTile * sizeof(LeafT);
-  const int64_t row = (int64_t)blockIdx.x * kTile + txn;
-  const bool valid = row < n;
-#ifdef FD_FOREST_PROFILE
-  unsigned long long p_walk = 0, p_leaf = 0, p_own = 0, p_sync = 0;
-#endif
-  FD_PROF_T(p_t0);
-
-  stage_chunk_asm(blob, bufA, chunk_stride, kWG3 / 64);  // chunk 0 lands while the tile loads
-  int anynan = 0;
-  const int ncopy = ld < nf ? ld : nf;
-  {
-    const int q = tid >> 8;  // the four threads sharing `txn` load every 4th column
-    float* Xs = reinterpret_cast<float*>(lbase);
-    if (valid) {
-      const float* xr = X + row * (int64_t)ld;
-      for (int f = q; f < ncopy; f += 4) {
-        const float v = xr[f];
-        Xs[f * kTile + txn] = v;
-        anynan |= (v != v);
-      }
-      for (int f = ncopy + q; f < nf; f += 4) Xs[f * kTile + txn] = __builtin_nanf("");
-      anynan |= (ncopy < nf);
-    } else {
-      for (int f = q; f < nf; f += 4) Xs[f * kTile + txn] = 0.f;
-    }
-    if (gg == 0)
-      lds_store<LeafT>(accL + txn * sizeof(LeafT),
-                       (KIND == FD_FOREST_XGB_BINARY_LOGISTIC) ? (LeafT)base_margin : (LeafT)0);
-  }
-  dma_wait();  // chunk 0 (published by tile_any's barrier)
-  const bool tile_nan =
-      tile_any(anynan, reinterpret_cast<uint32_t*>(lbase + (accL - s0) + kTile * sizeof(LeafT)), kWG3 / 64);
-  FD_PROF_T(p_t1);
-
-  for (int k = 0; k < n_chunks; ++k) {
-    FD_PROF_T(q0);
-    const uint32_t cur = (k & 1) ? bufB : bufA;
-    if (k + 1 < n_chunks)
-      stage_chunk_asm(blob + (size_t)(k + 1) * chunk_stride, (k & 1) ? bufA : bufB, chunk_stride, kWG3 / 64);
-    // owner of chunk k-1 adds its leaf values in tree order
-    if (k > 0 && gg == ((k - 1) & 3)) {
-      const uint32_t lv = ((k - 1) & 1) ? lvB : lvA;
-      LeafT acc = lds_load<LeafT>(accL + txn * sizeof(LeafT));
-#pragma unroll
-      for (int c = 0; c < CH; ++c) acc += lds_load<LeafT>(lv + (c * kTile + txn) * sizeof(LeafT));
-      lds_store<LeafT>(accL + txn * sizeof(LeafT), acc);
-    }
-    FD_PROF_T(q1);
-    uint32_t slots[TPG];
-    if (tile_nan)
-      walk3<D, TPG, LeafT, true>(cur, gg, lane4, slots);
-    else
-      walk3<D, TPG, LeafT, false>(cur, gg, lane4, slots);
-#ifdef FD_FOREST_PROFILE
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-    FD_PROF_T(q2);
-    const uint32_t lv = (k & 1) ? lvB : lvA;
-#pragma unroll
-    for (int j = 0; j < TPG; ++j) {
-      const int c = gg * TPG + j;
-      const uint32_t tb = cur + (uint32_t)c * TB;
-      const uint32_t slot = slots[j];
-      lds_store<LeafT>(lv + (c * kTile + txn) * sizeof(LeafT), lds_load<LeafT>(tb + NL * 8u + slot * sizeof(LeafT)));
-      if (out_leaf != nullptr && valid) {
-        const int tg = k * CH + c;
-        if (tg < n_trees) out_leaf[row * n_trees + tg] = leaf_ids[(size_t)tg * NL + slot];
-      }
-    }
-    FD_PROF_T(q3);
-    dma_wait();
-    __syncthreads();  // chunk k+1 landed; lv[k&1] complete; owner of k-1 done with lv[(k-1)&1]
-    FD_PROF_T(q4);
-    FD_PROF_ADD(p_own, q0, q1);
-    FD_PROF_ADD(p_walk, q1, q2);
-    FD_PROF_ADD(p_leaf, q2, q3);
-    FD_PROF_ADD(p_sync, q3, q4);
-  }
-#ifdef FD_FOREST_PROFILE
-  if (lane == 0 && blockIdx.x < 256) {
-    FD_PROF_T(p_t2);
-    unsigned long long* o = g_prof + ((size_t)blockIdx.x * 16 + wave) * 8;
-    o[0] = p_t1 - p_t0; o[1] = p_walk; o[2] = p_leaf; o[3] = p_own; o[4] = p_sync; o[5] = p_t2 - p_t0;
-    o[6] = p_t0; o[7] = 0;
-  }
-#endif
-  const int last = n_chunks - 1;
-  if (gg != (last & 3)) return;
-  LeafT acc = lds_load<LeafT>(accL + txn * sizeof(LeafT));
-  {
-    const uint32_t lv = (last & 1) ? lvB : lvA;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) acc += lds_load<LeafT>(lv + (c * kTile + txn) * sizeof(LeafT));
-  }
-  if (valid) write_outputs<KIND, LeafT>(acc, row, if_offset, if_denom, out_prob, out_raw);
+  constexpr Layout LAY = Layout::kThreshold;
+  constexpr const float* thr = nullptr;
+  constexpr const int32_t* thr_off = nullptr;
+  constexpr const LeafT* leaves = nullptr;
+#include "forest_tile_body.h"
 }
-
-// ------------------------------------------------------------------------------------------------
-// forest_kernel4 (depth <= 8, binned layout): kernel 3's structure with 4-byte nodes.
-//
-// The prologue replaces every feature value by its bin: the count of the feature's distinct split
-// thresholds that are <= x (branchless binary lifting over the sorted table, staged in LDS when it
-// fits), stored as the u32 word bin << 16 (missing/NaN: 0xFFFF << 16). A node word is
-// j << 16 | feature * 1024 | default_left, so "x < t_j" is "bin <= j" is ONE unsigned compare
-// word(x) <= node, the feature-row address is (node & 0xFC00) | lane, and a node's two children are
-// one 8-byte pair read: per level one ds_read_b32 (feature) and one ds_read_b64 (children).
 
 template <int D, int CH, typename LeafT, int KIND>
 __global__ void __launch_bounds__(kWG3)
@@ -621,140 +521,11 @@ forest_kernel4(const float* __restrict__ X, int64_t n, int ld, int nf, const cha
                const float* __restrict__ thr, const int32_t* __restrict__ thr_off, int bin_steps,
                float base_margin, double if_offset, double if_denom, double* __restrict__ out_prob,
                double* __restrict__ out_raw, int32_t* __restrict__ out_leaf) {
-  constexpr int TPG = CH / 4;
-  constexpr int NL = 1 << D;
-  constexpr uint32_t TB = (4u + (uint32_t)sizeof(LeafT)) << D;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const uint32_t sdyn = (uint32_t)(size_t)((lds_char*)smem);
-  const uint32_t s0 = (sdyn + 1023u) & ~1023u;
-  char* const lbase = smem + (s0 - sdyn);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int gg = wave >> 2;
-  const int txn = ((wave & 3) << 6) + lane;
-  const uint32_t lane4 = s0 + (uint32_t)txn * 4u;
-  const uint32_t xbytes = (uint32_t)nf * 1024u;
-  const uint32_t bufA = s0 + xbytes, bufB = bufA + (uint32_t)chunk_stride;
-  const uint32_t lvA = bufB + (uint32_t)chunk_stride;
-  const uint32_t lvB = lvA + CH * kTile * sizeof(LeafT);
-  const uint32_t accL = lvB + CH * kTile * sizeof(LeafT);
-  const int64_t row = (int64_t)blockIdx.x * kTile + txn;
-  const bool valid = row < n;
-#ifdef FD_FOREST_PROFILE
-  unsigned long long p_walk = 0, p_leaf = 0, p_own = 0, p_sync = 0;
-#endif
-  FD_PROF_T(p_t0);
-
-  stage_chunk_asm(blob, bufA, chunk_stride, kWG3 / 64);  // chunk 0 lands while the tile is binned
-  // threshold tables: into LDS over bufB + lv (dead until chunk 1 / the first leaf store) if they fit
-  const int n_thr = thr_off[nf];
-  const bool tbl_lds = (uint32_t)n_thr * 4u <= accL - bufB;
-  if (tbl_lds) {
-    float* tl = reinterpret_cast<float*>(lbase + (bufB - s0));
-    for (int i = tid; i < n_thr; i += kWG3) tl[i] = thr[i];
-    __syncthreads();
-  }
-  int anynan = 0;
-  const int ncopy = ld < nf ? ld : nf;
-  {
-    const int q = tid >> 8;  // the four threads sharing `txn` bin every 4th column
-    uint32_t* Xs = reinterpret_cast<uint32_t*>(lbase);
-    const float* xr = X + row * (int64_t)ld;
-    for (int f = q; f < nf; f += 4) {
-      uint32_t w = 0;
-      if (valid) {
-        const float v = f < ncopy ? xr[f] : __builtin_nanf("");  // DMatrix: missing column = NaN
-        if (v != v) {
-          w = 0xFFFF0000u;
-          anynan = 1;
-        } else {
-          const int o = thr_off[f], cnt = thr_off[f + 1] - o;
-          const uint32_t b = tbl_lds ? bin_of<true>(v, nullptr, bufB + (uint32_t)o * 4u, cnt, lift_steps(cnt))
-                                     : bin_of<false>(v, thr + o, 0u, cnt, lift_steps(cnt));
-          w = b << 16;
-        }
-      }
-      Xs[f * kTile + txn] = w;
-    }
-    if (gg == 0)
-      lds_store<LeafT>(accL + txn * sizeof(LeafT),
-                       (KIND == FD_FOREST_XGB_BINARY_LOGISTIC) ? (LeafT)base_margin : (LeafT)0);
-  }
-  dma_wait();  // chunk 0 (published by tile_any's barrier)
-  const bool tile_nan =
-      tile_any(anynan, reinterpret_cast<uint32_t*>(lbase + (accL - s0) + kTile * sizeof(LeafT)), kWG3 / 64);
-  FD_PROF_T(p_t1);
-
-  for (int k = 0; k < n_chunks; ++k) {
-    FD_PROF_T(q0);
-    const uint32_t cur = (k & 1) ? bufB : bufA;
-    if (k + 1 < n_chunks)
-      stage_chunk_asm(blob + (size_t)(k + 1) * chunk_stride, (k & 1) ? bufA : bufB, chunk_stride, kWG3 / 64);
-    if (k > 0 && gg == ((k - 1) & 3)) {  // owner of chunk k-1 adds its leaf values in tree order
-      const uint32_t lv = ((k - 1) & 1) ? lvB : lvA;
-      LeafT acc = lds_load<LeafT>(accL + txn * sizeof(LeafT));
-#pragma unroll
-      for (int c = 0; c < CH; ++c) acc += lds_load<LeafT>(lv + (c * kTile + txn) * sizeof(LeafT));
-      lds_store<LeafT>(accL + txn * sizeof(LeafT), acc);
-    }
-    FD_PROF_T(q1);
-    uint32_t slots[TPG];
-    if (tile_nan)
-      walk4<D, TPG, LeafT, true>(cur, gg, lane4, slots);
-    else
-      walk4<D, TPG, LeafT, false>(cur, gg, lane4, slots);
-#ifdef FD_FOREST_PROFILE
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-    FD_PROF_T(q2);
-    const uint32_t lv = (k & 1) ? lvB : lvA;
-#pragma unroll
-    for (int j = 0; j < TPG; ++j) {
-      const int c = gg * TPG + j;
-      const uint32_t tb = cur + (uint32_t)c * TB;
-      lds_store<LeafT>(lv + (c * kTile + txn) * sizeof(LeafT),
-                       lds_load<LeafT>(tb + NL * 4u + slots[j] * sizeof(LeafT)));
-      if (out_leaf != nullptr && valid) {
-        const int tg = k * CH + c;
-        if (tg < n_trees) out_leaf[row * n_trees + tg] = leaf_ids[(size_t)tg * NL + slots[j]];
-      }
-    }
-    FD_PROF_T(q3);
-    dma_wait();
-    __syncthreads();  // chunk k+1 landed; lv[k&1] complete; owner of k-1 done with lv[(k-1)&1]
-    FD_PROF_T(q4);
-    FD_PROF_ADD(p_own, q0, q1);
-    FD_PROF_ADD(p_walk, q1, q2);
-    FD_PROF_ADD(p_leaf, q2, q3);
-    FD_PROF_ADD(p_sync, q3, q4);
-  }
-#ifdef FD_FOREST_PROFILE
-  if (lane == 0 && blockIdx.x < 256) {
-    FD_PROF_T(p_t2);
-    unsigned long long* o = g_prof + ((size_t)blockIdx.x * 16 + wave) * 8;
-    o[0] = p_t1 - p_t0; o[1] = p_walk; o[2] = p_leaf; o[3] = p_own; o[4] = p_sync; o[5] = p_t2 - p_t0;
-    o[6] = p_t0; o[7] = 0;
-  }
-#endif
-  const int last = n_chunks - 1;
-  if (gg != (last & 3)) return;
-  LeafT acc = lds_load<LeafT>(accL + txn * sizeof(LeafT));
-  {
-    const uint32_t lv = (last & 1) ? lvB : lvA;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) acc += lds_load<LeafT>(lv + (c * kTile + txn) * sizeof(LeafT));
-  }
-  if (valid) write_outputs<KIND, LeafT>(acc, row, if_offset, if_denom, out_prob, out_raw);
+  constexpr Layout LAY = Layout::kBinned;
+  constexpr const LeafT* leaves = nullptr;
+#include "forest_tile_body.h"
 }
 
-// ------------------------------------------------------------------------------------------------
-// forest_kernel6 (depth <= 8, binned nodes): kernel 4 with node-only chunks. The staged chunk holds
-// only the CH trees' node words (1 KiB per depth-8 tree instead of 2-3 KiB with the leaves), so the
-// same LDS budget stages more trees per chunk: CH = 24 for XGBoost (TPG = 6 independent walks per
-// wave instead of 4) and 16 for the f64-leaf IsolationForest (instead of 8). The walk is bound by the
-// LDS round-trip latency of its dependent chains, not by LDS cycles (PMC: LDS array ~50 % busy, VALU
-// ~35 %), so more chains per wave is the lever. After the walk each lane reads its TPG leaf values
-// from the global [tree][2^D] array (L2-resident: 0.5 MiB for 500 x depth 8) with all loads in
-// flight together; the owner pass and the tree-order sum are kernel 4's.
 template <int D, int CH, typename LeafT, int KIND>
 __global__ void __launch_bounds__(kWG3)
 forest_kernel6(const float* __restrict__ X, int64_t n, int ld, int nf, const char* __restrict__ blob,
@@ -762,129 +533,8 @@ forest_kernel6(const float* __restrict__ X, int64_t n, int ld, int nf, const cha
                const float* __restrict__ thr, const int32_t* __restrict__ thr_off, int bin_steps,
                float base_margin, double if_offset, double if_denom, double* __restrict__ out_prob,
                double* __restrict__ out_raw, int32_t* __restrict__ out_leaf, const LeafT* __restrict__ leaves) {
-  constexpr int TPG = CH / 4;
-  constexpr int NL = 1 << D;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const uint32_t sdyn = (uint32_t)(size_t)((lds_char*)smem);
-  const uint32_t s0 = (sdyn + 1023u) & ~1023u;
-  char* const lbase = smem + (s0 - sdyn);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int gg = wave >> 2;
-  const int txn = ((wave & 3) << 6) + lane;
-  const uint32_t lane4 = s0 + (uint32_t)txn * 4u;
-  const uint32_t xbytes = (uint32_t)nf * 1024u;
-  const uint32_t bufA = s0 + xbytes, bufB = bufA + (uint32_t)chunk_stride;
-  const uint32_t lvA = bufB + (uint32_t)chunk_stride;
-  const uint32_t lvB = lvA + CH * kTile * sizeof(LeafT);
-  const uint32_t accL = lvB + CH * kTile * sizeof(LeafT);
-  const int64_t row = (int64_t)blockIdx.x * kTile + txn;
-  const bool valid = row < n;
-#ifdef FD_FOREST_PROFILE
-  unsigned long long p_walk = 0, p_leaf = 0, p_own = 0, p_sync = 0;
-#endif
-  FD_PROF_T(p_t0);
-
-  stage_chunk_asm(blob, bufA, chunk_stride, kWG3 / 64);  // chunk 0 lands while the tile is binned
-  // threshold tables: into LDS over bufB + lv (dead until chunk 1 / the first leaf store) if they fit
-  const int n_thr = thr_off[nf];
-  const bool tbl_lds = (uint32_t)n_thr * 4u <= accL - bufB;
-  if (tbl_lds) {
-    float* tl = reinterpret_cast<float*>(lbase + (bufB - s0));
-    for (int i = tid; i < n_thr; i += kWG3) tl[i] = thr[i];
-    __syncthreads();
-  }
-  int anynan = 0;
-  const int ncopy = ld < nf ? ld : nf;
-  {
-    const int q = tid >> 8;  // the four threads sharing `txn` bin every 4th column
-    uint32_t* Xs = reinterpret_cast<uint32_t*>(lbase);
-    const float* xr = X + row * (int64_t)ld;
-    for (int f = q; f < nf; f += 4) {
-      uint32_t w = 0;
-      if (valid) {
-        const float v = f < ncopy ? xr[f] : __builtin_nanf("");  // DMatrix: missing column = NaN
-        if (v != v) {
-          w = 0xFFFF0000u;
-          anynan = 1;
-        } else {
-          const int o = thr_off[f], cnt = thr_off[f + 1] - o;
-          const uint32_t b = tbl_lds ? bin_of<true>(v, nullptr, bufB + (uint32_t)o * 4u, cnt, lift_steps(cnt))
-                                     : bin_of<false>(v, thr + o, 0u, cnt, lift_steps(cnt));
-          w = b << 16;
-        }
-      }
-      Xs[f * kTile + txn] = w;
-    }
-    if (gg == 0)
-      lds_store<LeafT>(accL + txn * sizeof(LeafT),
-                       (KIND == FD_FOREST_XGB_BINARY_LOGISTIC) ? (LeafT)base_margin : (LeafT)0);
-  }
-  dma_wait();  // chunk 0 (published by tile_any's barrier)
-  const bool tile_nan =
-      tile_any(anynan, reinterpret_cast<uint32_t*>(lbase + (accL - s0) + kTile * sizeof(LeafT)), kWG3 / 64);
-  FD_PROF_T(p_t1);
-
-  for (int k = 0; k < n_chunks; ++k) {
-    FD_PROF_T(q0);
-    const uint32_t cur = (k & 1) ? bufB : bufA;
-    if (k + 1 < n_chunks)
-      stage_chunk_asm(blob + (size_t)(k + 1) * chunk_stride, (k & 1) ? bufA : bufB, chunk_stride, kWG3 / 64);
-    if (k > 0 && gg == ((k - 1) & 3)) {  // owner of chunk k-1 adds its leaf values in tree order
-      const uint32_t lv = ((k - 1) & 1) ? lvB : lvA;
-      LeafT acc = lds_load<LeafT>(accL + txn * sizeof(LeafT));
-#pragma unroll
-      for (int c = 0; c < CH; ++c) acc += lds_load<LeafT>(lv + (c * kTile + txn) * sizeof(LeafT));
-      lds_store<LeafT>(accL + txn * sizeof(LeafT), acc);
-    }
-    FD_PROF_T(q1);
-    uint32_t slots[TPG];
-    if (tile_nan)
-      walk4<D, TPG, LeafT, true, true>(cur, gg, lane4, slots);
-    else
-      walk4<D, TPG, LeafT, false, true>(cur, gg, lane4, slots);
-#ifdef FD_FOREST_PROFILE
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-    const uint32_t lv = (k & 1) ? lvB : lvA;
-    LeafT lval[TPG];  // leaf values from global memory (L2-resident), all TPG loads in flight together
-#pragma unroll
-    for (int j = 0; j < TPG; ++j) lval[j] = leaves[((size_t)k * CH + gg * TPG + j) * NL + slots[j]];
-#pragma unroll
-    for (int j = 0; j < TPG; ++j) {
-      const int c = gg * TPG + j;
-      lds_store<LeafT>(lv + (c * kTile + txn) * sizeof(LeafT), lval[j]);
-      if (out_leaf != nullptr && valid) {
-        const int tg = k * CH + c;
-        if (tg < n_trees) out_leaf[row * n_trees + tg] = leaf_ids[(size_t)tg * NL + slots[j]];
-      }
-    }
-    FD_PROF_T(q2);
-    FD_PROF_T(q3);
-    dma_wait();
-    __syncthreads();  // chunk k+1 landed; lv[k&1] complete; owner of k-1 done with lv[(k-1)&1]
-    FD_PROF_T(q4);
-    FD_PROF_ADD(p_own, q0, q1);
-    FD_PROF_ADD(p_walk, q1, q2);
-    FD_PROF_ADD(p_leaf, q2, q3);
-    FD_PROF_ADD(p_sync, q3, q4);
-  }
-#ifdef FD_FOREST_PROFILE
-  if (lane == 0 && blockIdx.x < 256) {
-    FD_PROF_T(p_t2);
-    unsigned long long* o = g_prof + ((size_t)blockIdx.x * 16 + wave) * 8;
-    o[0] = p_t1 - p_t0; o[1] = p_walk; o[2] = p_leaf; o[3] = p_own; o[4] = p_sync; o[5] = p_t2 - p_t0;
-    o[6] = p_t0; o[7] = 0;
-  }
-#endif
-  const int last = n_chunks - 1;
-  if (gg != (last & 3)) return;
-  LeafT acc = lds_load<LeafT>(accL + txn * sizeof(LeafT));
-  {
-    const uint32_t lv = (last & 1) ? lvB : lvA;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) acc += lds_load<LeafT>(lv + (c * kTile + txn) * sizeof(LeafT));
-  }
-  if (valid) write_outputs<KIND, LeafT>(acc, row, if_offset, if_denom, out_prob, out_raw);
+  constexpr Layout LAY = Layout::kNodeOnly;
+#include "forest_tile_body.h"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1239,152 +889,65 @@ split_sum_kernel(const LeafT* __restrict__ leaves, int64_t n, int n_trees, float
 // ------------------------------------------------------------------------------------------------
 // dispatch
 
-using KernelFn = void (*)(const float*, int64_t, int, int, const char*, int, int, const int32_t*, int,
-                          float, double, double, double*, double*, int32_t*);
+// A runtime (depth, chunk) pair -> the template instantiation. Each kernel family lists the values it
+// is built for; with_constants() hands the matching pair to a generic lambda as integral constants.
+template <int... Vs>
+using Ints = std::integer_sequence<int, Vs...>;
 
-template <typename LeafT, int KIND, int CH>
-KernelFn pick1_ch(int D) {
-  switch (D) {
-    case 1: return forest_kernel1<1, CH, LeafT, KIND>;
-    case 2: return forest_kernel1<2, CH, LeafT, KIND>;
-    case 3: return forest_kernel1<3, CH, LeafT, KIND>;
-    case 4: return forest_kernel1<4, CH, LeafT, KIND>;
-    case 5: return forest_kernel1<5, CH, LeafT, KIND>;
-    case 6: return forest_kernel1<6, CH, LeafT, KIND>;
-    case 7: return forest_kernel1<7, CH, LeafT, KIND>;
-    case 8: return forest_kernel1<8, CH, LeafT, KIND>;
-    case 9: return forest_kernel1<9, CH, LeafT, KIND>;
-    case 10: return forest_kernel1<10, CH, LeafT, KIND>;
-    default: return nullptr;
-  }
+using Depths8 = Ints<1, 2, 3, 4, 5, 6, 7, 8>;          // kernels 3, 4, 6, split_walk_kernel
+using Depths10 = Ints<1, 2, 3, 4, 5, 6, 7, 8, 9, 10>;  // kernel 1
+using Chunks1 = Ints<1, 2, 4, 8, 12, 16>;              // kernel 1
+using ChunksTile = Ints<4, 8, 12, 16>;                 // kernels 3, 4, split_walk_kernel, split_walk_pair_kernel
+using ChunksNodeOnly = Ints<16, 24, 32>;               // kernel 6
+
+// f(std::integral_constant<int, V>) for the V of the list equal to v; false when the list has no such value
+template <int... Vs, typename F>
+bool with_constant(Ints<Vs...>, int v, F&& f) {
+  return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+template <typename As, typename Bs, typename F>
+bool with_constants(As, int a, Bs, int b, F&& f) {
+  bool hit = false;
+  with_constant(As{}, a, [&](auto ca) { hit = with_constant(Bs{}, b, [&](auto cb) { f(ca, cb); }); });
+  return hit;
 }
 
-template <typename LeafT, int KIND>
-KernelFn pick1(int D, int CH) {
-  switch (CH) {
-    case 1: return pick1_ch<LeafT, KIND, 1>(D);
-    case 2: return pick1_ch<LeafT, KIND, 2>(D);
-    case 4: return pick1_ch<LeafT, KIND, 4>(D);
-    case 8: return pick1_ch<LeafT, KIND, 8>(D);
-    case 12: return pick1_ch<LeafT, KIND, 12>(D);
-    case 16: return pick1_ch<LeafT, KIND, 16>(D);
-    default: return nullptr;
-  }
+// f(LeafT{}, kind constant) for the forest's kind: f32 leaves for XGBoost, f64 for the IsolationForest
+template <typename F>
+void with_kind(const PackedForest& pf, F&& f) {
+  if (pf.kind == FD_FOREST_XGB_BINARY_LOGISTIC)
+    f(float{}, std::integral_constant<int, FD_FOREST_XGB_BINARY_LOGISTIC>{});
+  else
+    f(double{}, std::integral_constant<int, FD_FOREST_SKLEARN_IFOREST>{});
+}
+int timing_kind(const PackedForest& pf) {
+  return pf.kind == FD_FOREST_XGB_BINARY_LOGISTIC ? FD_TIMING_XGB : FD_TIMING_IFOREST;
+}
+size_t leaf_bytes(const PackedForest& pf) {
+  return pf.kind == FD_FOREST_XGB_BINARY_LOGISTIC ? sizeof(float) : sizeof(double);
 }
 
-template <typename LeafT, int KIND, int CH>
-KernelFn pick3_ch(int D) {
-  switch (D) {
-    case 1: return forest_kernel3<1, CH, LeafT, KIND>;
-    case 2: return forest_kernel3<2, CH, LeafT, KIND>;
-    case 3: return forest_kernel3<3, CH, LeafT, KIND>;
-    case 4: return forest_kernel3<4, CH, LeafT, KIND>;
-    case 5: return forest_kernel3<5, CH, LeafT, KIND>;
-    case 6: return forest_kernel3<6, CH, LeafT, KIND>;
-    case 7: return forest_kernel3<7, CH, LeafT, KIND>;
-    case 8: return forest_kernel3<8, CH, LeafT, KIND>;
-    default: return nullptr;
-  }
+// lets `fn` be launched with `lds` bytes of dynamic LDS (the runtime takes the kernel as an untyped address)
+template <typename... P>
+void allow_dynamic_lds(void (*fn)(P...), size_t lds) {
+  FD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 }
 
-template <typename LeafT, int KIND>
-KernelFn pick3(int D, int CH) {
-  switch (CH) {
-    case 4: return pick3_ch<LeafT, KIND, 4>(D);
-    case 8: return pick3_ch<LeafT, KIND, 8>(D);
-    case 12: return pick3_ch<LeafT, KIND, 12>(D);
-    case 16: return pick3_ch<LeafT, KIND, 16>(D);
-    default: return nullptr;
-  }
-}
-
-using KernelFn4 = void (*)(const float*, int64_t, int, int, const char*, int, int, const int32_t*, int,
-                           const float*, const int32_t*, int, float, double, double, double*, double*, int32_t*);
-
-template <typename LeafT, int KIND, int CH>
-KernelFn4 pick4_ch(int D) {
-  switch (D) {
-    case 1: return forest_kernel4<1, CH, LeafT, KIND>;
-    case 2: return forest_kernel4<2, CH, LeafT, KIND>;
-    case 3: return forest_kernel4<3, CH, LeafT, KIND>;
-    case 4: return forest_kernel4<4, CH, LeafT, KIND>;
-    case 5: return forest_kernel4<5, CH, LeafT, KIND>;
-    case 6: return forest_kernel4<6, CH, LeafT, KIND>;
-    case 7: return forest_kernel4<7, CH, LeafT, KIND>;
-    case 8: return forest_kernel4<8, CH, LeafT, KIND>;
-    default: return nullptr;
-  }
-}
-
-template <typename LeafT, int KIND>
-KernelFn4 pick4(int D, int CH) {
-  switch (CH) {
-    case 4: return pick4_ch<LeafT, KIND, 4>(D);
-    case 8: return pick4_ch<LeafT, KIND, 8>(D);
-    case 12: return pick4_ch<LeafT, KIND, 12>(D);
-    case 16: return pick4_ch<LeafT, KIND, 16>(D);
-    default: return nullptr;
-  }
-}
-
-template <int D, typename LeafT>
-void* pick_split_ch(int CH) {
-  switch (CH) {
-    case 4: return (void*)split_walk_kernel<D, 4, LeafT>;
-    case 8: return (void*)split_walk_kernel<D, 8, LeafT>;
-    case 12: return (void*)split_walk_kernel<D, 12, LeafT>;
-    case 16: return (void*)split_walk_kernel<D, 16, LeafT>;
-    default: return nullptr;
-  }
-}
-
-template <typename LeafT>
-void* pick_split(int D, int CH) {
-  switch (D) {
-    case 1: return pick_split_ch<1, LeafT>(CH);
-    case 2: return pick_split_ch<2, LeafT>(CH);
-    case 3: return pick_split_ch<3, LeafT>(CH);
-    case 4: return pick_split_ch<4, LeafT>(CH);
-    case 5: return pick_split_ch<5, LeafT>(CH);
-    case 6: return pick_split_ch<6, LeafT>(CH);
-    case 7: return pick_split_ch<7, LeafT>(CH);
-    case 8: return pick_split_ch<8, LeafT>(CH);
-    default: return nullptr;
-  }
-}
-
-using KernelFn6 = void (*)(const float*, int64_t, int, int, const char*, int, int, const int32_t*, int,
-                           const float*, const int32_t*, int, float, double, double, double*, double*, int32_t*,
-                           const void*);
-
-template <typename LeafT, int KIND, int CH>
-KernelFn6 pick6_ch(int D) {
-  switch (D) {
-    case 1: return (KernelFn6)forest_kernel6<1, CH, LeafT, KIND>;
-    case 2: return (KernelFn6)forest_kernel6<2, CH, LeafT, KIND>;
-    case 3: return (KernelFn6)forest_kernel6<3, CH, LeafT, KIND>;
-    case 4: return (KernelFn6)forest_kernel6<4, CH, LeafT, KIND>;
-    case 5: return (KernelFn6)forest_kernel6<5, CH, LeafT, KIND>;
-    case 6: return (KernelFn6)forest_kernel6<6, CH, LeafT, KIND>;
-    case 7: return (KernelFn6)forest_kernel6<7, CH, LeafT, KIND>;
-    case 8: return (KernelFn6)forest_kernel6<8, CH, LeafT, KIND>;
-    default: return nullptr;
-  }
-}
-
-template <typename LeafT, int KIND>
-KernelFn6 pick6(int D, int CH) {
-  switch (CH) {
-    case 16: return pick6_ch<LeafT, KIND, 16>(D);
-    case 24: return pick6_ch<LeafT, KIND, 24>(D);
-    case 32: return pick6_ch<LeafT, KIND, 32>(D);
-    default: return nullptr;
-  }
+// One forest kernel (tile kernels and kernel 1) over `blocks` tiles on the engine's stream: dynamic-LDS attribute,
+// timing event pair, launch, error check.
+template <typename... P, typename... A>
+void launch_forest_kernel(Engine& e, const PackedForest& pf, void (*fn)(P...), int threads, size_t lds, int64_t blocks,
+                        A... args) {
+  allow_dynamic_lds(fn, lds);
+  Engine::Timed* ev = e.timing ? e.next_event_pair(timing_kind(pf)) : nullptr;
+  if (ev) FD_HIP(hipEventRecord(ev->a, e.stream));
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(threads), lds, e.stream, args...);
+  FD_HIP(hipGetLastError());
+  if (ev) FD_HIP(hipEventRecord(ev->b, e.stream));
 }
 
 // small-batch launch: bin once, walk (tiles x chunk groups), sequential sum
 // stage 1: the forest's scratch for this batch (NaN tile flags zeroed when allocated, cleared after each use)
-template <typename LeafT>
 SplitBinArgs split_prepare(const PackedForest& pf, int64_t n, int64_t tiles, hipStream_t stream) {
   const int64_t n_pad = tiles * kTile;
   SplitScratch& sc = pf.split;  // per forest: two forests may run concurrently on different streams
@@ -1393,55 +956,69 @@ SplitBinArgs split_prepare(const PackedForest& pf, int64_t n, int64_t tiles, hip
     sc.nan.ensure((size_t)tiles * 4);
     FD_HIP(hipMemsetAsync(sc.nan.ptr, 0, sc.nan.bytes, stream));
   }
-  sc.leaves.ensure((size_t)pf.n_trees * n * sizeof(LeafT));
+  sc.leaves.ensure((size_t)pf.n_trees * n * leaf_bytes(pf));
   return SplitBinArgs{pf.b_thr.as<const float>(), pf.b_thr_off.as<const int32_t>(), sc.bins.as<uint32_t>(),
                       sc.nan.as<uint32_t>(), pf.num_feature};
 }
 
-// stage 3: walk (tiles x chunk groups) over the binned rows, then the sequential sum
-template <typename LeafT, int KIND>
-void split_walk_sum(const PackedForest& pf, int64_t n, double* d_prob, double* d_raw, int32_t* d_leaf, int64_t tiles,
-                    hipStream_t stream) {
-  const int64_t n_pad = tiles * kTile;
-  SplitScratch& sc = pf.split;
-  // chunk groups: enough workgroups to cover the CUs (tiles x groups >= 256)
+// one forest's side of a walk launch over `tiles` tiles (the scratch is split_prepare's). Chunk groups: enough
+// workgroups to cover the CUs (tiles x groups >= 256)
+SplitWalkArgs split_walk_args(const PackedForest& pf, int64_t tiles) {
   const int want = (int)std::max<int64_t>(1, (256 + tiles - 1) / tiles);
-  const int cpg = std::max(1, (pf.b_n_chunks + want - 1) / want);
-  const int groups = (pf.b_n_chunks + cpg - 1) / cpg;
-  void* fn = pick_split<LeafT>(pf.depth, pf.b_chunk);
-  FD_REQUIRE(fn != nullptr, FD_ERR_UNSUPPORTED, "no split forest kernel for this depth/chunk");
-  const size_t lds = (size_t)pf.num_feature * 1024 + 2 * pf.b_chunk_stride + 1024;
-  FD_REQUIRE(lds <= kLdsBudget, FD_ERR_UNSUPPORTED, "split forest kernel exceeds the LDS budget");
-  FD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  using WalkFn = void (*)(const uint32_t*, int64_t, int64_t, int, const uint32_t*, const char*, int, int, int,
-                          const int32_t*, int, LeafT*, int32_t*);
-  hipLaunchKernelGGL((WalkFn)fn, dim3((unsigned)tiles, (unsigned)groups), dim3(kWG3), lds, stream,
-                     sc.bins.as<const uint32_t>(), n, n_pad, pf.num_feature, sc.nan.as<const uint32_t>(),
-                     pf.b_blob.as<const char>(), pf.b_n_chunks, (int)pf.b_chunk_stride, cpg,
-                     pf.leaf_ids.as<const int32_t>(), pf.n_trees, sc.leaves.as<LeafT>(), d_leaf);
-  FD_HIP(hipGetLastError());
-  hipLaunchKernelGGL((split_sum_kernel<KIND, LeafT>), dim3((unsigned)((n + kSumRows - 1) / kSumRows)), dim3(256), 0,
-                     stream, sc.leaves.as<const LeafT>(), n, pf.n_trees, pf.base_margin, pf.if_offset,
-                     pf.if_denominator, d_prob, d_raw, sc.nan.as<uint32_t>());
-  FD_HIP(hipGetLastError());
+  SplitWalkArgs w{};
+  w.bins = pf.split.bins.as<const uint32_t>();
+  w.tile_nan = pf.split.nan.as<const uint32_t>();
+  w.blob = pf.b_blob.as<const char>();
+  w.n_chunks = pf.b_n_chunks;
+  w.chunk_stride = (int)pf.b_chunk_stride;
+  w.cpg = std::max(1, (pf.b_n_chunks + want - 1) / want);
+  w.groups = (pf.b_n_chunks + w.cpg - 1) / w.cpg;
+  w.leaf_ids = pf.leaf_ids.as<const int32_t>();
+  w.n_trees = pf.n_trees;
+  w.leaves = pf.split.leaves.ptr;
+  return w;
 }
 
-template <typename LeafT, int KIND>
-void launch_split(Engine& e, const PackedForest& pf, const float* d_X, int64_t n, int32_t ld, double* d_prob,
-                  double* d_raw, int32_t* d_leaf, int64_t tiles, hipStream_t stream) {
-  (void)e;
-  const SplitBinArgs a = split_prepare<LeafT>(pf, n, tiles, stream);
+// stage 3: walk (tiles x chunk groups) over the binned rows, then the sequential sum
+void split_walk_sum(const PackedForest& pf, int64_t n, double* d_prob, double* d_raw, int32_t* d_leaf, int64_t tiles,
+                    hipStream_t stream) {
+  const SplitWalkArgs w = split_walk_args(pf, tiles);
+  const size_t lds = (size_t)pf.num_feature * 1024 + 2 * pf.b_chunk_stride + 1024;
+  with_kind(pf, [&](auto leaf, auto kind) {
+    using LeafT = decltype(leaf);
+    const bool found = with_constants(Depths8{}, pf.depth, ChunksTile{}, pf.b_chunk, [&](auto d, auto ch) {
+      auto* fn = split_walk_kernel<decltype(d)::value, decltype(ch)::value, LeafT>;
+      FD_REQUIRE(lds <= kLdsBudget, FD_ERR_UNSUPPORTED, "split forest kernel exceeds the LDS budget");
+      allow_dynamic_lds(fn, lds);
+      hipLaunchKernelGGL(fn, dim3((unsigned)tiles, (unsigned)w.groups), dim3(kWG3), lds, stream, w.bins, n,
+                         tiles * kTile, pf.num_feature, w.tile_nan, w.blob, w.n_chunks, w.chunk_stride, w.cpg,
+                         w.leaf_ids, w.n_trees, pf.split.leaves.as<LeafT>(), d_leaf);
+      FD_HIP(hipGetLastError());
+    });
+    FD_REQUIRE(found, FD_ERR_UNSUPPORTED, "no split forest kernel for this depth/chunk");
+    hipLaunchKernelGGL((split_sum_kernel<decltype(kind)::value, LeafT>),
+                       dim3((unsigned)((n + kSumRows - 1) / kSumRows)), dim3(256), 0, stream,
+                       pf.split.leaves.as<const LeafT>(), n, pf.n_trees, pf.base_margin, pf.if_offset,
+                       pf.if_denominator, d_prob, d_raw, pf.split.nan.as<uint32_t>());
+    FD_HIP(hipGetLastError());
+  });
+}
+
+void launch_split(const PackedForest& pf, const float* d_X, int64_t n, int32_t ld, double* d_prob, double* d_raw,
+                  int32_t* d_leaf, int64_t tiles, hipStream_t stream) {
+  const SplitBinArgs a = split_prepare(pf, n, tiles, stream);
   hipLaunchKernelGGL(split_bin_kernel, dim3((unsigned)(tiles * kTile / kSplitBin), (unsigned)pf.num_feature),
                      dim3(kSplitBin), 0, stream, d_X, n, tiles * kTile, (int)ld, pf.num_feature, a.thr, a.thr_off,
                      pf.bin_steps, a.bins, a.tile_nan);
   FD_HIP(hipGetLastError());
-  split_walk_sum<LeafT, KIND>(pf, n, d_prob, d_raw, d_leaf, tiles, stream);
+  split_walk_sum(pf, n, d_prob, d_raw, d_leaf, tiles, stream);
 }
 
+// the tree-split path: for forests with the binned layout; option 6 forces it, auto takes it below kSplitTiles tiles
+bool split_capable(const PackedForest& pf) { return pf.binned && pf.depth <= 8 && pf.b_chunk % 4 == 0; }
 bool split_path(const Engine& e, const PackedForest& pf, int64_t n) {
   const int64_t blocks = (n + kTile - 1) / kTile;
-  const bool ok_split = pf.binned && pf.depth <= 8 && pf.b_chunk % 4 == 0;
-  return ok_split && (e.forest_variant == 6 || (e.forest_variant == 0 && blocks < kSplitTiles));
+  return split_capable(pf) && (e.forest_variant == 6 || (e.forest_variant == 0 && blocks < kSplitTiles));
 }
 
 }  // namespace
@@ -1469,68 +1046,38 @@ bool launch_forest_pair(Engine& e, const PackedForest& pa, const PackedForest& p
   FD_REQUIRE(d_X && d_prob_a && d_prob_b && ld > 0, FD_ERR_INVALID_ARG, "null buffer or bad ld");
   const int64_t tiles = (n + kTile - 1) / kTile;
   const hipStream_t st = e.stream;
-  const bool xa = pa.kind == FD_FOREST_XGB_BINARY_LOGISTIC, xb = pb.kind == FD_FOREST_XGB_BINARY_LOGISTIC;
-  Engine::Timed* ev = e.timing ? e.next_event_pair(xa ? FD_TIMING_XGB : FD_TIMING_IFOREST) : nullptr;
+  Engine::Timed* ev = e.timing ? e.next_event_pair(timing_kind(pa)) : nullptr;
   if (ev) FD_HIP(hipEventRecord(ev->a, st));  // the first forest's time includes the shared binning
-  const SplitBinArgs a = xa ? split_prepare<float>(pa, n, tiles, st) : split_prepare<double>(pa, n, tiles, st);
-  const SplitBinArgs b = xb ? split_prepare<float>(pb, n, tiles, st) : split_prepare<double>(pb, n, tiles, st);
+  const SplitBinArgs a = split_prepare(pa, n, tiles, st);
+  const SplitBinArgs b = split_prepare(pb, n, tiles, st);
   hipLaunchKernelGGL(split_bin_pair_kernel, dim3((unsigned)(tiles * kTile / kSplitBin), (unsigned)(a.nf + b.nf)),
                      dim3(kSplitBin), 0, st, d_X, n, tiles * kTile, (int)ld, a, b);
   FD_HIP(hipGetLastError());
-  if (xa)
-    split_walk_sum<float, FD_FOREST_XGB_BINARY_LOGISTIC>(pa, n, d_prob_a, nullptr, nullptr, tiles, st);
-  else
-    split_walk_sum<double, FD_FOREST_SKLEARN_IFOREST>(pa, n, d_prob_a, nullptr, nullptr, tiles, st);
+  split_walk_sum(pa, n, d_prob_a, nullptr, nullptr, tiles, st);
   if (ev) FD_HIP(hipEventRecord(ev->b, st));
-  ev = e.timing ? e.next_event_pair(xb ? FD_TIMING_XGB : FD_TIMING_IFOREST) : nullptr;
+  ev = e.timing ? e.next_event_pair(timing_kind(pb)) : nullptr;
   if (ev) FD_HIP(hipEventRecord(ev->a, st));
-  if (xb)
-    split_walk_sum<float, FD_FOREST_XGB_BINARY_LOGISTIC>(pb, n, d_prob_b, nullptr, nullptr, tiles, st);
-  else
-    split_walk_sum<double, FD_FOREST_SKLEARN_IFOREST>(pb, n, d_prob_b, nullptr, nullptr, tiles, st);
+  split_walk_sum(pb, n, d_prob_b, nullptr, nullptr, tiles, st);
   if (ev) FD_HIP(hipEventRecord(ev->b, st));
   return true;
 }
 
 namespace {
-template <int CHX>
-const void* pick_walk_pair_i(int chi) {
-  switch (chi) {
-    case 4: return (const void*)split_walk_pair_kernel<8, CHX, 8, 4>;
-    case 8: return (const void*)split_walk_pair_kernel<8, CHX, 8, 8>;
-    case 12: return (const void*)split_walk_pair_kernel<8, CHX, 8, 12>;
-    case 16: return (const void*)split_walk_pair_kernel<8, CHX, 8, 16>;
-    default: return nullptr;
-  }
-}
-const void* pick_walk_pair(int chx, int chi) {
-  switch (chx) {
-    case 4: return pick_walk_pair_i<4>(chi);
-    case 8: return pick_walk_pair_i<8>(chi);
-    case 12: return pick_walk_pair_i<12>(chi);
-    case 16: return pick_walk_pair_i<16>(chi);
-    default: return nullptr;
-  }
-}
-
-// chunk groups of one forest's walk over `tiles` tiles: enough workgroups to cover the CUs (as split_walk_sum)
-void walk_groups(const PackedForest& pf, int64_t tiles, int& cpg, int& groups) {
-  const int want = (int)std::max<int64_t>(1, (256 + tiles - 1) / tiles);
-  cpg = std::max(1, (pf.b_n_chunks + want - 1) / want);
-  groups = (pf.b_n_chunks + cpg - 1) / cpg;
-}
+using WalkPairFn = void (*)(int64_t, int64_t, int, SplitWalkArgs, SplitWalkArgs);
 
 // The pair path's forests (XGBoost first) and its walk kernel, or false when it does not apply
 bool pair_blend_plan(const Engine& e, const PackedForest& p1, const PackedForest& p2, int64_t n,
-                     const PackedForest*& xf, const PackedForest*& ff, const void*& walk, size_t& lds) {
+                     const PackedForest*& xf, const PackedForest*& ff, WalkPairFn& walk, size_t& lds) {
   if (n == 0 || &p1 == &p2 || !split_path(e, p1, n) || !split_path(e, p2, n)) return false;
   const bool x1 = p1.kind == FD_FOREST_XGB_BINARY_LOGISTIC, x2 = p2.kind == FD_FOREST_XGB_BINARY_LOGISTIC;
   if (x1 == x2) return false;  // one XGBoost and one IsolationForest
   const PackedForest& X = x1 ? p1 : p2;
   const PackedForest& F = x1 ? p2 : p1;
   if (X.depth != 8 || F.depth != 8 || X.num_feature != F.num_feature) return false;
-  walk = pick_walk_pair(X.b_chunk, F.b_chunk);
-  if (!walk) return false;
+  const bool found = with_constants(ChunksTile{}, X.b_chunk, ChunksTile{}, F.b_chunk, [&](auto chx, auto chf) {
+    walk = split_walk_pair_kernel<8, decltype(chx)::value, 8, decltype(chf)::value>;
+  });
+  if (!found) return false;
   lds = (size_t)X.num_feature * 1024 + 2 * std::max(X.b_chunk_stride, F.b_chunk_stride) + 1024;
   if (lds > kLdsBudget) return false;
   xf = &X;
@@ -1544,12 +1091,12 @@ bool forest_pair_prebin(Engine& e, const PackedForest& p1, const PackedForest& p
   PreBin& pb = e.prebin;
   pb.want = pb.done = false;
   const PackedForest *xf = nullptr, *ff = nullptr;
-  const void* walk = nullptr;
+  WalkPairFn walk = nullptr;
   size_t lds = 0;
   if (!e.latency_prebin || !pair_blend_plan(e, p1, p2, n, xf, ff, walk, lds)) return false;
   const int64_t tiles = (n + kTile - 1) / kTile;
-  const SplitBinArgs a = split_prepare<float>(*xf, n, tiles, e.stream);
-  const SplitBinArgs b = split_prepare<double>(*ff, n, tiles, e.stream);
+  const SplitBinArgs a = split_prepare(*xf, n, tiles, e.stream);
+  const SplitBinArgs b = split_prepare(*ff, n, tiles, e.stream);
   pb.thr[0] = a.thr, pb.thr[1] = b.thr;
   pb.thr_off[0] = a.thr_off, pb.thr_off[1] = b.thr_off;
   pb.bins[0] = a.bins, pb.bins[1] = b.bins;
@@ -1572,7 +1119,7 @@ bool launch_forest_pair_blend(Engine& e, const PackedForest& p1, const PackedFor
                               int32_t ld, const BlendConsts& bc, const double* const* cols, int pos1, int pos2,
                               double* dfp, double* dconf, uint8_t* ddec, uint8_t* drisk, hipEvent_t before_blend) {
   const PackedForest *xf = nullptr, *ff = nullptr;
-  const void* walk = nullptr;
+  WalkPairFn walk = nullptr;
   size_t lds = 0;
   // the bins of an LSTM launch that binned these vectors for this pair (PreBin), consumed here
   const bool prebinned = e.prebin.done && e.prebin.X == d_X && e.prebin.n == n && e.prebin.ld == ld;
@@ -1582,14 +1129,13 @@ bool launch_forest_pair_blend(Engine& e, const PackedForest& p1, const PackedFor
   if (!pair_blend_plan(e, p1, p2, n, xf, ff, walk, lds)) return false;
   const PackedForest& X = *xf;
   const PackedForest& F = *ff;
-  const int nf = X.num_feature;
   FD_REQUIRE(d_X && dfp && cols && ld > 0, FD_ERR_INVALID_ARG, "null buffer or bad ld");
   const int64_t tiles = (n + kTile - 1) / kTile, n_pad = tiles * kTile;
   const hipStream_t st = e.stream;
   Engine::Timed* ev = e.timing ? e.next_event_pair(FD_TIMING_XGB) : nullptr;  // the pair's launches
   if (ev) FD_HIP(hipEventRecord(ev->a, st));
-  const SplitBinArgs a = split_prepare<float>(X, n, tiles, st);
-  const SplitBinArgs b = split_prepare<double>(F, n, tiles, st);
+  const SplitBinArgs a = split_prepare(X, n, tiles, st);
+  const SplitBinArgs b = split_prepare(F, n, tiles, st);
   if (prebinned && pre_fx == &X && pre_ff == &F) {
     ++e.prebin_total;
   } else {
@@ -1597,28 +1143,11 @@ bool launch_forest_pair_blend(Engine& e, const PackedForest& p1, const PackedFor
                        dim3(kSplitBin), 0, st, d_X, n, n_pad, (int)ld, a, b);
     FD_HIP(hipGetLastError());
   }
-  SplitWalkArgs wx{}, wf{};
-  wx.bins = a.bins;
-  wx.tile_nan = a.tile_nan;
-  wx.blob = X.b_blob.as<const char>();
-  wx.n_chunks = X.b_n_chunks;
-  wx.chunk_stride = (int)X.b_chunk_stride;
-  walk_groups(X, tiles, wx.cpg, wx.groups);
-  wx.leaf_ids = X.leaf_ids.as<const int32_t>();
-  wx.n_trees = X.n_trees;
-  wx.leaves = X.split.leaves.ptr;
-  wf.bins = b.bins;
-  wf.tile_nan = b.tile_nan;
-  wf.blob = F.b_blob.as<const char>();
-  wf.n_chunks = F.b_n_chunks;
-  wf.chunk_stride = (int)F.b_chunk_stride;
-  walk_groups(F, tiles, wf.cpg, wf.groups);
-  wf.leaf_ids = F.leaf_ids.as<const int32_t>();
-  wf.n_trees = F.n_trees;
-  wf.leaves = F.split.leaves.ptr;
-  FD_HIP(hipFuncSetAttribute(walk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  void* wargs[] = {&n, const_cast<int64_t*>(&n_pad), const_cast<int*>(&nf), &wx, &wf};
-  FD_HIP(hipLaunchKernel(walk, dim3((unsigned)tiles, (unsigned)(wx.groups + wf.groups)), dim3(kWG3), wargs, lds, st));
+  const SplitWalkArgs wx = split_walk_args(X, tiles), wf = split_walk_args(F, tiles);
+  allow_dynamic_lds(walk, lds);
+  hipLaunchKernelGGL(walk, dim3((unsigned)tiles, (unsigned)(wx.groups + wf.groups)), dim3(kWG3), lds, st, n, n_pad,
+                     X.num_feature, wx, wf);
+  FD_HIP(hipGetLastError());
   PairBlendArgs pa{};
   pa.blend = bc;
   for (int m = 0; m < bc.n_models; ++m) pa.cols.p[m] = cols[m];
@@ -1645,26 +1174,20 @@ void launch_forest(Engine& e, const PackedForest& pf, const float* d_X, int64_t 
                    double* d_prob, double* d_raw, int32_t* d_leaf, hipStream_t stream) {
   FD_REQUIRE(d_X && d_prob && ld > 0, FD_ERR_INVALID_ARG, "null buffer or bad ld");
   if (n == 0) return;
-  const bool xgb = pf.kind == FD_FOREST_XGB_BINARY_LOGISTIC;
-  const size_t leaf_sz = xgb ? sizeof(float) : sizeof(double);
   const int64_t blocks = (n + kTile - 1) / kTile;
   FD_REQUIRE(blocks < (1ll << 31), FD_ERR_INVALID_ARG, "batch too large");
   const int v = e.forest_variant;
   FD_REQUIRE(v == 0 || v == 1 || v == 2 || v == 3 || v == 6 || v == 8, FD_ERR_INVALID_ARG,
              "forest_kernel option must be 0, 1, 2, 3, 6 or 8");
-  Engine::Timed* ev = nullptr;
 
   // small batches: tree-split latency path (option 6 forces it; auto below 128 tiles)
-  const bool ok_split = pf.binned && pf.depth <= 8 && pf.b_chunk % 4 == 0;
-  if (v == 6) FD_REQUIRE(ok_split, FD_ERR_UNSUPPORTED, "the split forest path needs the binned layout (depth <= 8)");
-  if ((v == 6 || (v == 0 && blocks < kSplitTiles)) && ok_split) {
+  if (v == 6)
+    FD_REQUIRE(split_capable(pf), FD_ERR_UNSUPPORTED, "the split forest path needs the binned layout (depth <= 8)");
+  if (split_path(e, pf, n)) {
     const hipStream_t st = stream ? stream : e.stream;
-    ev = e.timing ? e.next_event_pair(xgb ? FD_TIMING_XGB : FD_TIMING_IFOREST) : nullptr;
+    Engine::Timed* ev = e.timing ? e.next_event_pair(timing_kind(pf)) : nullptr;
     if (ev) FD_HIP(hipEventRecord(ev->a, st));
-    if (xgb)
-      launch_split<float, FD_FOREST_XGB_BINARY_LOGISTIC>(e, pf, d_X, n, ld, d_prob, d_raw, d_leaf, blocks, st);
-    else
-      launch_split<double, FD_FOREST_SKLEARN_IFOREST>(e, pf, d_X, n, ld, d_prob, d_raw, d_leaf, blocks, st);
+    launch_split(pf, d_X, n, ld, d_prob, d_raw, d_leaf, blocks, st);
     if (ev) FD_HIP(hipEventRecord(ev->b, st));
     return;
   }
@@ -1676,75 +1199,65 @@ void launch_forest(Engine& e, const PackedForest& pf, const float* d_X, int64_t 
     if (slot >= 0 && slot < kMaxSlots && launch_ensemble_single(e, slot, d_X, n, ld, d_prob, d_raw, stream)) return;
   }
 
-  // + 64 B: kernel 6's two item counters after the tile_any flags
-  const size_t lds6 = pf.n_chunk ? lds_bytes_kernel3(pf.num_feature, pf.n_chunk_stride, pf.n_chunk, leaf_sz) + 64 : 0;
-  const bool ok6 = pf.binned && pf.n_chunk > 0 && pf.depth <= 8 && lds6 <= kLdsBudget;
-  if (v == 8)
-    FD_REQUIRE(ok6, FD_ERR_UNSUPPORTED, "forest kernel 6 needs the binned node-only layout (depth <= 8)");
-  if ((v == 0 || v == 8) && ok6) {
-    KernelFn6 fn = xgb ? pick6<float, FD_FOREST_XGB_BINARY_LOGISTIC>(pf.depth, pf.n_chunk)
-                       : pick6<double, FD_FOREST_SKLEARN_IFOREST>(pf.depth, pf.n_chunk);
-    FD_REQUIRE(fn != nullptr, FD_ERR_UNSUPPORTED, "no forest kernel 6 for this depth/chunk");
-    FD_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds6));
-    ev = e.timing ? e.next_event_pair(xgb ? FD_TIMING_XGB : FD_TIMING_IFOREST) : nullptr;
-    if (ev) FD_HIP(hipEventRecord(ev->a, e.stream));
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kWG3), lds6, e.stream, d_X, n, (int)ld, pf.num_feature,
-                       pf.n_blob.as<const char>(), pf.n_n_chunks, (int)pf.n_chunk_stride,
-                       pf.leaf_ids.as<const int32_t>(), pf.n_trees, pf.b_thr.as<const float>(),
-                       pf.b_thr_off.as<const int32_t>(), pf.bin_steps, pf.base_margin, pf.if_offset,
-                       pf.if_denominator, d_prob, d_raw, d_leaf, (const void*)pf.n_leaves.ptr);
-    FD_HIP(hipGetLastError());
-    if (ev) FD_HIP(hipEventRecord(ev->b, e.stream));
-    return;
-  }
+  // the tile kernels: 6, else 4, else 3, else 1
+  with_kind(pf, [&](auto leaf, auto kind) {
+    using LeafT = decltype(leaf);
+    constexpr int KIND = decltype(kind)::value;
+    const int nf = pf.num_feature;
+    const int32_t* leaf_ids = pf.leaf_ids.as<const int32_t>();
+    const float* thr = pf.b_thr.as<const float>();
+    const int32_t* thr_off = pf.b_thr_off.as<const int32_t>();
 
-  const size_t lds4 = pf.binned ? lds_bytes_kernel4(pf.num_feature, pf.b_chunk_stride, pf.b_chunk, leaf_sz) : 0;
-  const bool ok4 = pf.binned && pf.depth <= 8 && pf.b_chunk % 4 == 0 && lds4 <= kLdsBudget;
-  if (v == 3) FD_REQUIRE(ok4, FD_ERR_UNSUPPORTED, "forest kernel 4 needs the binned layout (depth <= 8)");
-  if ((v == 0 || v == 3) && ok4) {
-    KernelFn4 fn = xgb ? pick4<float, FD_FOREST_XGB_BINARY_LOGISTIC>(pf.depth, pf.b_chunk)
-                       : pick4<double, FD_FOREST_SKLEARN_IFOREST>(pf.depth, pf.b_chunk);
-    FD_REQUIRE(fn != nullptr, FD_ERR_UNSUPPORTED, "no forest kernel 4 for this depth/chunk");
-    FD_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4));
-    ev = e.timing ? e.next_event_pair(xgb ? FD_TIMING_XGB : FD_TIMING_IFOREST) : nullptr;
-    if (ev) FD_HIP(hipEventRecord(ev->a, e.stream));
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kWG3), lds4, e.stream, d_X, n, (int)ld, pf.num_feature,
-                       pf.b_blob.as<const char>(), pf.b_n_chunks, (int)pf.b_chunk_stride,
-                       pf.leaf_ids.as<const int32_t>(), pf.n_trees, pf.b_thr.as<const float>(),
-                       pf.b_thr_off.as<const int32_t>(), pf.bin_steps, pf.base_margin, pf.if_offset,
-                       pf.if_denominator, d_prob, d_raw, d_leaf);
-    FD_HIP(hipGetLastError());
-    if (ev) FD_HIP(hipEventRecord(ev->b, e.stream));
-    return;
-  }
+    // + 64 B: unused padding. The kernel does not touch it; it stays only so that the forests within 64 B of the
+    // LDS budget keep falling to kernel 4 as before. Follow-up: drop it together with that selection change.
+    const size_t lds6 = pf.n_chunk ? lds_bytes_tile(nf, pf.n_chunk_stride, pf.n_chunk, sizeof(LeafT)) + 64 : 0;
+    const bool ok6 = pf.binned && pf.n_chunk > 0 && pf.depth <= 8 && lds6 <= kLdsBudget;
+    if (v == 8) FD_REQUIRE(ok6, FD_ERR_UNSUPPORTED, "forest kernel 6 needs the binned node-only layout (depth <= 8)");
+    if ((v == 0 || v == 8) && ok6) {
+      const bool found = with_constants(Depths8{}, pf.depth, ChunksNodeOnly{}, pf.n_chunk, [&](auto d, auto ch) {
+        launch_forest_kernel(e, pf, forest_kernel6<decltype(d)::value, decltype(ch)::value, LeafT, KIND>, kWG3, lds6,
+                           blocks, d_X, n, (int)ld, nf, pf.n_blob.as<const char>(), pf.n_n_chunks,
+                           (int)pf.n_chunk_stride, leaf_ids, pf.n_trees, thr, thr_off, pf.bin_steps, pf.base_margin,
+                           pf.if_offset, pf.if_denominator, d_prob, d_raw, d_leaf, pf.n_leaves.as<const LeafT>());
+      });
+      FD_REQUIRE(found, FD_ERR_UNSUPPORTED, "no forest kernel 6 for this depth/chunk");
+      return;
+    }
 
-  KernelFn fn = nullptr;
-  int threads = kTile;
-  size_t lds = 0;
-  const size_t lds3 = lds_bytes_kernel3(pf.num_feature, pf.chunk_stride, pf.chunk, leaf_sz);
-  const bool ok3 = pf.depth <= 8 && pf.chunk % 4 == 0 && lds3 <= kLdsBudget;
-  if (v == 2) FD_REQUIRE(ok3, FD_ERR_UNSUPPORTED, "forest kernel 3 does not fit this forest");
-  if (v != 1 && ok3) {
-    fn = xgb ? pick3<float, FD_FOREST_XGB_BINARY_LOGISTIC>(pf.depth, pf.chunk)
-             : pick3<double, FD_FOREST_SKLEARN_IFOREST>(pf.depth, pf.chunk);
-    threads = kWG3;
-    lds = lds3;
-  }
-  if (!fn) {
-    fn = xgb ? pick1<float, FD_FOREST_XGB_BINARY_LOGISTIC>(pf.depth, pf.chunk)
-             : pick1<double, FD_FOREST_SKLEARN_IFOREST>(pf.depth, pf.chunk);
-    lds = lds_bytes_kernel1(pf.num_feature, pf.chunk_stride);
-  }
-  FD_REQUIRE(fn != nullptr, FD_ERR_UNSUPPORTED, "no forest kernel for this depth/chunk");
-  FD_REQUIRE(lds <= kLdsBudget, FD_ERR_UNSUPPORTED, "LDS budget exceeded");
-  FD_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  ev = e.timing ? e.next_event_pair(xgb ? FD_TIMING_XGB : FD_TIMING_IFOREST) : nullptr;
-  if (ev) FD_HIP(hipEventRecord(ev->a, e.stream));
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(threads), lds, e.stream, d_X, n, (int)ld, pf.num_feature,
-                     pf.blob.as<const char>(), pf.n_chunks, (int)pf.chunk_stride, pf.leaf_ids.as<const int32_t>(),
-                     pf.n_trees, pf.base_margin, pf.if_offset, pf.if_denominator, d_prob, d_raw, d_leaf);
-  FD_HIP(hipGetLastError());
-  if (ev) FD_HIP(hipEventRecord(ev->b, e.stream));
+    const size_t lds4 = pf.binned ? lds_bytes_tile(nf, pf.b_chunk_stride, pf.b_chunk, sizeof(LeafT)) : 0;
+    const bool ok4 = split_capable(pf) && lds4 <= kLdsBudget;
+    if (v == 3) FD_REQUIRE(ok4, FD_ERR_UNSUPPORTED, "forest kernel 4 needs the binned layout (depth <= 8)");
+    if ((v == 0 || v == 3) && ok4) {
+      const bool found = with_constants(Depths8{}, pf.depth, ChunksTile{}, pf.b_chunk, [&](auto d, auto ch) {
+        launch_forest_kernel(e, pf, forest_kernel4<decltype(d)::value, decltype(ch)::value, LeafT, KIND>, kWG3, lds4,
+                           blocks, d_X, n, (int)ld, nf, pf.b_blob.as<const char>(), pf.b_n_chunks,
+                           (int)pf.b_chunk_stride, leaf_ids, pf.n_trees, thr, thr_off, pf.bin_steps, pf.base_margin,
+                           pf.if_offset, pf.if_denominator, d_prob, d_raw, d_leaf);
+      });
+      FD_REQUIRE(found, FD_ERR_UNSUPPORTED, "no forest kernel 4 for this depth/chunk");
+      return;
+    }
+
+    // the threshold layout: kernel 3, or kernel 1 (deep trees, option 1)
+    auto launch = [&](auto* fn, int threads, size_t lds) {
+      FD_REQUIRE(lds <= kLdsBudget, FD_ERR_UNSUPPORTED, "LDS budget exceeded");
+      launch_forest_kernel(e, pf, fn, threads, lds, blocks, d_X, n, (int)ld, nf, pf.blob.as<const char>(), pf.n_chunks,
+                         (int)pf.chunk_stride, leaf_ids, pf.n_trees, pf.base_margin, pf.if_offset, pf.if_denominator,
+                         d_prob, d_raw, d_leaf);
+    };
+    const size_t lds3 = lds_bytes_tile(nf, pf.chunk_stride, pf.chunk, sizeof(LeafT));
+    const bool ok3 = pf.depth <= 8 && pf.chunk % 4 == 0 && lds3 <= kLdsBudget;
+    if (v == 2) FD_REQUIRE(ok3, FD_ERR_UNSUPPORTED, "forest kernel 3 does not fit this forest");
+    if (v != 1 && ok3 && with_constants(Depths8{}, pf.depth, ChunksTile{}, pf.chunk, [&](auto d, auto ch) {
+          launch(forest_kernel3<decltype(d)::value, decltype(ch)::value, LeafT, KIND>, kWG3, lds3);
+        }))
+      return;
+    const bool found = with_constants(Depths10{}, pf.depth, Chunks1{}, pf.chunk, [&](auto d, auto ch) {
+      launch(forest_kernel1<decltype(d)::value, decltype(ch)::value, LeafT, KIND>, kTile,
+             lds_bytes_kernel1(nf, pf.chunk_stride));
+    });
+    FD_REQUIRE(found, FD_ERR_UNSUPPORTED, "no forest kernel for this depth/chunk");
+  });
 }
 
 }  // namespace fd

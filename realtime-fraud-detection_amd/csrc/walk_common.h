@@ -32,7 +32,7 @@ __device__ __forceinline__ void lds_store(uint32_t addr, T v) {
 
 // Tile-wide OR that is also the prologue barrier. Hand-rolled (per-wave ballot -> one LDS word per
 // wave) because __syncthreads_or pulls 256 B of STATIC LDS into the kernel, which shifts the
-// dynamic-LDS base and breaks the 1 KiB-aligned feature-tile addressing of forest_kernel3.
+// dynamic-LDS base and breaks the 1 KiB-aligned feature-tile addressing of the tile kernels.
 __device__ __forceinline__ bool tile_any(int pred, uint32_t* flags, int nwaves) {
   const unsigned long long b = __ballot(pred);
   if ((threadIdx.x & 63) == 0) flags[threadIdx.x >> 6] = (b != 0ull) ? 1u : 0u;

@@ -15,11 +15,13 @@ PROB_TOL = 1e-5  # north_star: fraud probabilities within 1e-5 absolute
 
 
 def _xgb_case(engine, slot, n, n_trees, depth, nf, seed, p_leaf=0.0, nan_frac=0.0, ld=None, base_score=0.5,
-              max_bin=256):
+              max_bin=256, forest_out=None):
     X = synth.feature_matrix(n, nf, seed=seed, nan_frac=nan_frac)
     doc = synth.xgboost_doc(n_trees, depth, nf, synth.feature_matrix(512, nf, seed=seed + 1), seed=seed + 2,
                             p_leaf=p_leaf, base_score=base_score, max_bin=max_bin)
     fa = xgboost_from_json_doc(doc)
+    if forest_out is not None:
+        forest_out.append(fa)
     if ld is not None and ld < nf:
         X = np.ascontiguousarray(X[:, :ld])
     engine.load_forest(slot, fa)
@@ -137,15 +139,25 @@ def test_device_pointer_path_matches_host_path(engine):
     np.testing.assert_array_equal(dp.cpu().numpy(), host)
 
 
-@pytest.mark.parametrize("depth", [1, 2, 3, 4, 6, 8])
-@pytest.mark.parametrize("variant", [3, 8])
-def test_kernel4_depths(engine, depth, variant):
-    """The binned 1024-thread kernel (option 3) and its node-only-chunk form with leaves from global memory
-    (option 8, kernel 6) across depths, ragged trees, NaNs, odd tree counts."""
+@pytest.mark.parametrize("depth,nf", [(1, 21), (2, 21), (3, 21), (4, 21), (6, 21), (8, 21), (8, 64)],
+                         ids=["1", "2", "3", "4", "6", "8", "8-64features"])
+@pytest.mark.parametrize("variant", [2, 3, 8])
+def test_kernel4_depths(engine, depth, nf, variant):
+    """The three layouts of the shared 1024-thread tile kernel body — threshold (option 2, kernel 3), binned
+    (option 3, kernel 4) and binned node-only chunks with leaves from global memory (option 8, kernel 6) — across
+    depths, ragged trees, NaNs, odd tree counts. The LDS budget stages 16 / 16 / 32 trees per chunk at 21 features
+    and 8 / 12 / 16 at 64, so the 64-feature case runs the small-chunk instantiations; the chunk sizes of the
+    threshold and binned layouts are asserted (the host packer reports them; the node-only layout's is not
+    exposed, it follows from the same LDS arithmetic)."""
     engine.set_option("forest_kernel", variant)
     try:
-        prob, raw, leaf, rp, rm, rl = _xgb_case(engine, 1, 777, 45, depth, 21, seed=190 + depth, p_leaf=0.2,
-                                                nan_frac=0.02)
+        fa = []
+        prob, raw, leaf, rp, rm, rl = _xgb_case(engine, 1, 777, 45, depth, nf, seed=190 + depth, p_leaf=0.2,
+                                                nan_frac=0.02, forest_out=fa)
+        if depth == 8:
+            from fdengine.engine import pack_forest_binned_host, pack_forest_host
+            assert pack_forest_host(fa[0])[-1].chunk == (16 if nf == 21 else 8)
+            assert pack_forest_binned_host(fa[0])[-1].chunk == (16 if nf == 21 else 12)
         np.testing.assert_array_equal(leaf, rl)
         np.testing.assert_array_equal(raw.astype(np.float32), rm)
         assert np.abs(prob - rp).max() <= PROB_TOL

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Phase-cycle breakdown of forest_kernel3 on the config-2 workload (profiling build of the engine,
-lib/libfdengine_prof.so, -DFD_FOREST_PROFILE). Per wave of the first 256 workgroups: prologue, walk,
-leaf store, owner sum, barrier wait, total (s_memtime cycles)."""
+"""Phase-cycle breakdown of the tile kernels' shared body on the config-2 workload (profiling build of the
+engine, lib/libfdengine_prof.so, -DFD_FOREST_PROFILE; VARIANT=2 / 3 / 8: kernel 3 / 4 / 6). Per wave of the
+first 256 workgroups: prologue, walk, leaf store (kernel 6: with its global leaf loads), owner sum, barrier
+wait, total (s_memtime cycles)."""
 import ctypes as C
 import os
 import sys
