@@ -43,7 +43,7 @@ enum fd_status {
   FD_ERR_IO = 6, /* snapshot file missing / truncated / corrupt (checksum) */
 };
 
-/* Forest kinds: the two tree model types on the path. */
+/* Forest kinds: the tree model types on the path. */
 enum fd_forest_kind {
   /* xgboost 2.0.3 gbtree, objective binary:logistic
      (ml/models/model_manager.py:157-161 load, :309-311 predict_proba[:,1]) */
@@ -51,6 +51,12 @@ enum fd_forest_kind {
   /* scikit-learn IsolationForest, decision_function then 1/(1+e^s)
      (ml/models/model_manager.py:197-200 load, :338-346 predict) */
   FD_FOREST_SKLEARN_IFOREST = 2,
+  /* scikit-learn RandomForestClassifier / ExtraTreesClassifier / DecisionTreeClassifier, two classes:
+     predict_proba(X)[:, 1] (ml/models/model_manager.py:338-346, the branch for models with predict_proba).
+     Comparison and NaN rules are sklearn's, as for the IsolationForest (default_left = missing_go_to_left);
+     leaf_value = tree_.value[node, 0, 1] (f64); raw = the f64 sum of the leaf values in tree order,
+     prob = raw / n_trees. Served by the sparse layout only (fd_pack_forest_sparse_host). */
+  FD_FOREST_SKLEARN_PROBA = 3,
 };
 
 typedef struct fd_engine fd_engine;
@@ -133,8 +139,9 @@ int fd_forest_info(fd_engine* eng, int slot, int32_t* n_trees, int32_t* depth, i
 
 /* Replaces _predict_xgboost (:309-311) / _predict_sklearn (:338-346) for a batch.
    d_X: n x ld row-major f32 (what XGBoost's DMatrix / sklearn's validate_data cast the f64 vector to).
-   d_prob: P(fraud) per row (XGB: f32 sigmoid widened; IF: 1/(1+exp(decision_function))).
-   d_raw (optional): XGB margin / IF summed path length.
+   d_prob: P(fraud) per row (XGB: f32 sigmoid widened; IF: 1/(1+exp(decision_function)); sklearn classifier:
+   predict_proba[:, 1]).
+   d_raw (optional): XGB margin / IF summed path length / classifier: summed leaf values.
    d_leaf (optional): n x n_trees original leaf node ids (xgboost pred_leaf / sklearn apply). */
 int fd_forest_predict_device(fd_engine* eng, int slot, const float* d_X, int64_t n, int32_t ld,
                              double* d_prob, double* d_raw, int32_t* d_leaf);
@@ -170,6 +177,36 @@ int fd_pack_forest_host(const fd_forest_params* params, const fd_tree_arrays* tr
 int fd_pack_forest_binned_host(const fd_forest_params* params, const fd_tree_arrays* trees, void* blob,
                                int64_t blob_cap, float* thresholds, int64_t thr_cap, int32_t* offsets,
                                fd_pack_info* info);
+
+/* Sparse (pointer) layout, host-only repack: trees of ANY depth and any kind keep their shape (no padding). It is the
+   only layout of FD_FOREST_SKLEARN_PROBA and of forests deeper than 10 levels (fd_load_forest picks it for them;
+   fd_forest_info then reports the true depth), and what engine option forest_kernel = 11 walks for any forest.
+     nodes: n_nodes records of 8 bytes {f32 t, u32 meta}, "go left <=> x < t" (sklearn's (double)x <= thr rewritten
+       as for the other layouts). Records 0 .. n_trees-1 are the roots in tree order; behind them each tree's other
+       nodes in breadth-first order, so a node's two children are adjacent records.
+       internal node: meta = child | feature << 24 | default_left << 30   (bit 31 clear); child = index of the LEFT
+                      child's record in `nodes` (forest-global, 24 bits), the right child is child + 1
+       leaf:          meta = 1 << 31 | ordinal; ordinal = forest-global leaf number (trees in order; within a tree
+                      its root first, then its other records in order)
+     leaf_values: n_leaves values by ordinal, f32 (XGBoost) or f64 (both sklearn kinds); info->leaf_bytes is 4 or 8
+     leaf_ids:    n_leaves original node ids by ordinal (xgboost pred_leaf / sklearn apply)
+   A tree whose root is a leaf, and a degenerate chain, are valid. Limits (FD_ERR_UNSUPPORTED, named in the message):
+   at most 2^24 nodes in the forest (the child field), num_feature <= 64 (the feature field; also the LDS tile).
+   FD_ERR_INVALID_ARG: a child index outside its tree, a node reached twice (a cycle or a shared subtree).
+   Call with NULL buffers to query sizes in *info; capacities are counted in records / values / ids. */
+typedef struct {
+  int32_t kind;
+  int32_t n_trees;
+  int32_t depth;      /* deepest leaf over all trees (a root leaf has depth 0) */
+  int32_t leaf_bytes; /* 4 or 8 */
+  int64_t n_nodes;
+  int64_t n_leaves;
+  float base_margin;  /* XGB: f32 margin seeded by base_score */
+  int32_t pad;
+} fd_sparse_info;
+int fd_pack_forest_sparse_host(const fd_forest_params* params, const fd_tree_arrays* trees, void* nodes,
+                               int64_t nodes_cap, void* leaf_values, int64_t values_cap, int32_t* leaf_ids,
+                               int64_t ids_cap, fd_sparse_info* info);
 
 /* ---------------------------------------------------------------- blend (a11-a13) */
 /* Replaces _calculate_model_confidence + _combine_predictions + _make_decision +
@@ -651,7 +688,8 @@ int fd_ingest_scalar_host(int32_t kind, const uint8_t* text, int32_t n, double* 
 /* ---------------------------------------------------------------- diagnostics */
 /* Per-launch device timing of the engine's hot kernels, measured with HIP events recorded on the
    launch stream around each kernel. fd_timing_read synchronises and returns the summed time (ms) and
-   count of the timed launches of `kind` (FD_TIMING_ALL: every kind) since the last fd_timing_reset. */
+   count of the timed launches of `kind` (FD_TIMING_ALL: every kind) since the last fd_timing_reset.
+   A forest launch counts under FD_TIMING_XGB for an XGBoost forest, FD_TIMING_IFOREST for both sklearn kinds. */
 enum fd_timing_kind { FD_TIMING_ALL = -1, FD_TIMING_XGB = 0, FD_TIMING_IFOREST = 1, FD_TIMING_FEATURES = 2,
                       FD_TIMING_BLEND = 3, FD_TIMING_ROUTE = 4, FD_TIMING_LSTM = 5,
                       FD_TIMING_WINDOWS = 6, FD_TIMING_INGEST = 7,
@@ -661,7 +699,11 @@ int fd_engine_set_timing(fd_engine* eng, int enable);
      "forest_kernel": 0 auto, 1 force the 256-thread kernel, 2 force the 1024-thread tree-split kernel
      on the threshold layout, 3 force the 1024-thread kernel on the binned layout, 6 force the tree-split
      small-batch path (auto takes it below 128 tiles of 256 transactions), 8 force the binned node-only-chunk
-     kernel (auto's choice when the forest has that layout); the variants measured slower were removed
+     kernel (auto's choice when the forest has that layout), 11 force the sparse-layout kernel (forest_sparse_kernel:
+     nodes read from global memory; its image is built on the first such launch for a forest that has the heap
+     layouts). A FD_FOREST_SKLEARN_PROBA forest or one deeper than 10 levels has the sparse layout only and takes
+     that kernel whatever this option says; the variants measured slower were removed (their numbers 4, 5, 7, 9
+     and 10 stay refused)
      "ensemble": 1 fused XGBoost + IsolationForest + blend kernel when applicable (default), 0 per-model kernels
      "ensemble_chunks": the fused kernel's chunk layout, 0 (default) auto: compact once the engine has RCCL
      communicators (fd_comm_init), else wide; 1 wide (24 XGBoost / 16 IsolationForest trees per chunk, 148 KB of
@@ -707,7 +749,9 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    ring's whole capacity K of prior events — their counts may be truncated at K; synchronises the engine's streams),
    "pipelined_batches" (batches through fd_score_batch_pipelined /
    fd_score_records_pipelined so far), "pipelined_compact_batches" (of those, scored by the fused ensemble kernel from
-   the compact 64-B rows: no vectors requested), "pipelined_slot_stream_batches" (of those, with the slot pass on
+   the compact 64-B rows: no vectors requested), "ensemble_single_launches" (fd_forest_predict batches scored by the
+   fused kernel over one forest), "forest_sparse_launches" (launches of the sparse-layout forest kernel),
+   "pipelined_slot_stream_batches" (of those, with the slot pass on
    its own stream), "pipelined_host_ns" (host nanoseconds inside fd_score_batch_pipelined), "sharded_steps" (fd_sharded_step calls), "rccl_ops" (RCCL operations the exchanges issued: sends, receives,
    all-gathers) and "sharded_host_ns_<phase>" (host
    nanoseconds inside fd_sharded_step by phase: "wait" the split sizes, "partition" / "counts" / "count_copy" the

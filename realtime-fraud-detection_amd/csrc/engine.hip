@@ -480,6 +480,9 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
   } else if (k == "ensemble_single_launches") {  // fd_forest_predict batches scored by the fused kernel over one
     // forest (probabilities, optionally raw scores; no leaf ids): config 2's timed kernel, ensemble_kernel<8,2>
     *value = (int64_t)e.ens_single_total;
+  } else if (k == "forest_sparse_launches") {  // launches of forest_sparse_kernel: predict_proba forests, forests
+    // deeper than 10 levels, and any forest under option forest_kernel = 11
+    *value = (int64_t)e.sparse_total;
   } else if (k == "latency_prebinned_batches") {  // latency pair launches that used the feature kernel's bins
     *value = (int64_t)e.prebin_total;
   } else if (k == "pipelined_split_batches") {  // of the compact ones: split rows (compact_vectors 2)
@@ -523,9 +526,10 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value) {
   FD_REQUIRE(key, FD_ERR_INVALID_ARG, "null key");
   const std::string k(key);
   if (k == "forest_kernel") {
-    // 0 auto; 1 / 2 / 3 / 8 force kernel 1 / 3 / 4 / 6; 6 the tree-split path (forest.hip launch_forest)
-    FD_REQUIRE(value == 0 || value == 1 || value == 2 || value == 3 || value == 6 || value == 8, FD_ERR_INVALID_ARG,
-               "forest_kernel must be 0, 1, 2, 3, 6 or 8");
+    // 0 auto; 1 / 2 / 3 / 8 force kernel 1 / 3 / 4 / 6; 6 the tree-split path; 11 the sparse-layout kernel
+    // (forest.hip launch_forest)
+    FD_REQUIRE(value == 0 || value == 1 || value == 2 || value == 3 || value == 6 || value == 8 || value == 11,
+               FD_ERR_INVALID_ARG, "forest_kernel must be 0, 1, 2, 3, 6, 8 or 11");
     e.forest_variant = (int)value;
   } else if (k == "ensemble") {  // 1 (default): fused forests + blend when applicable; 0: per-model kernels
     FD_REQUIRE(value == 0 || value == 1, FD_ERR_INVALID_ARG, "ensemble must be 0 or 1");
@@ -760,6 +764,35 @@ int fd_pack_forest_binned_host(const fd_forest_params* params, const fd_tree_arr
   FD_API_END
 }
 
+int fd_pack_forest_sparse_host(const fd_forest_params* params, const fd_tree_arrays* trees, void* nodes,
+                               int64_t nodes_cap, void* leaf_values, int64_t values_cap, int32_t* leaf_ids,
+                               int64_t ids_cap, fd_sparse_info* info) {
+  FD_API_BEGIN
+  FD_REQUIRE(params && trees && info, FD_ERR_INVALID_ARG, "null params/trees/info");
+  const fd::SparsePack sp = fd::pack_forest_sparse_host(*params, *trees);
+  *info = fd_sparse_info{};
+  info->kind = sp.kind;
+  info->n_trees = sp.n_trees;
+  info->depth = sp.depth;
+  info->leaf_bytes = sp.leaf_bytes;
+  info->n_nodes = sp.n_nodes;
+  info->n_leaves = sp.n_leaves;
+  info->base_margin = sp.base_margin;
+  if (nodes) {
+    FD_REQUIRE(nodes_cap >= sp.n_nodes, FD_ERR_INVALID_ARG, "node buffer too small");
+    std::memcpy(nodes, sp.nodes.data(), sp.nodes.size() * sizeof(uint32_t));
+  }
+  if (leaf_values) {
+    FD_REQUIRE(values_cap >= sp.n_leaves, FD_ERR_INVALID_ARG, "leaf value buffer too small");
+    std::memcpy(leaf_values, sp.leaf_val.data(), sp.leaf_val.size());
+  }
+  if (leaf_ids) {
+    FD_REQUIRE(ids_cap >= sp.n_leaves, FD_ERR_INVALID_ARG, "leaf id buffer too small");
+    std::memcpy(leaf_ids, sp.leaf_ids.data(), sp.leaf_ids.size() * sizeof(int32_t));
+  }
+  FD_API_END
+}
+
 int fd_load_xgboost_json(fd_engine* eng, int slot, const char* path) {
   FD_API_BEGIN
   FD_ENGINE_LOCK(eng);
@@ -830,6 +863,9 @@ int fd_unload_forest(fd_engine* eng, int slot) {
   pf.b_thr.release();
   pf.b_thr_off.release();
   for (auto* b : {&pf.split.bins, &pf.split.nan, &pf.split.leaves}) b->release();
+  for (auto* b : {&pf.sp.nodes, &pf.sp.leaf_val, &pf.sp.leaf_ids}) b->release();
+  pf.sp.gen = 0;
+  pf.sparse_only = false;
   pf.binned = false;
   pf.loaded = false;
   pf.gen = 0;  // any ensemble plan built over this slot is stale

@@ -894,7 +894,8 @@ bool build_plan(Engine& e, EnsemblePlan& P, int sa, int sb, bool wide) {
   int D = 0, nf = -1;
   for (const PackedForest* f : F) {
     if (!f) continue;
-    if (!f->binned || f->t_off.empty() || (nf >= 0 && f->num_feature != nf)) return false;
+    // (a sparse-only forest — predict_proba kind or deeper than the heaps — has no binned layout: per-model path)
+    if (f->sparse_only || !f->binned || f->t_off.empty() || (nf >= 0 && f->num_feature != nf)) return false;
     nf = f->num_feature;
     D = std::max(D, f->depth);
   }
@@ -1058,7 +1059,7 @@ bool select_pair(Engine& e, const fd_blend_params& p, const int32_t* slots, cons
   for (int m = 0; m < p.n_models; ++m) {
     if (present && !present[m]) continue;
     const int s = slots[m];
-    if (s < 0 || s >= kMaxSlots || !e.forests[s].loaded) return false;
+    if (s < 0 || s >= kMaxSlots || !e.forests[s].loaded || e.forests[s].sparse_only) return false;
     const int kind = e.forests[s].kind;
     if (kind == FD_FOREST_XGB_BINARY_LOGISTIC && q.sa < 0) {
       q.sa = s;
@@ -1175,7 +1176,7 @@ bool launch_ensemble_single(Engine& e, int slot, const float* dX, int64_t n, int
                             double* draw, hipStream_t stream) {
   if (!e.ensemble_on || e.forest_variant != 0 || n <= 0) return false;
   if ((n + kTile - 1) / kTile < kSplitTiles) return false;
-  if (slot < 0 || slot >= kMaxSlots || !e.forests[slot].loaded) return false;
+  if (slot < 0 || slot >= kMaxSlots || !e.forests[slot].loaded || e.forests[slot].sparse_only) return false;
   const bool xgb = e.forests[slot].kind == FD_FOREST_XGB_BINARY_LOGISTIC;
   const int sa = xgb ? slot : -1, sb = xgb ? -1 : slot;
   EnsemblePlan& P = e.ens1[slot];

@@ -57,7 +57,10 @@ __host__ __device__ constexpr int compact_src(int f) {
     if (kCompactSlot[k] == f) return k;
   return (f == 12 || f == 24 || f == 25 || f == 33 || f == 34) ? -2 : -1;
 }
-constexpr int kMaxDepth = 10;     // deepest tree the repacker accepts
+constexpr int kMaxDepth = 10;     // deepest tree the heap repacker accepts (deeper forests: the sparse layout)
+// Sparse (pointer) layout, forest_sparse.hip: a node's meta word holds a 24-bit forest-global node index (the left
+// child; the right child is the next record) or leaf ordinal, and a 6-bit feature
+constexpr int64_t kSparseMaxNodes = 1ll << 24;
 constexpr size_t kLdsBudget = 160 * 1024;  // LDS per CU (one workgroup per CU at 64k batches)
 constexpr int kMaxBins = 65534;   // distinct thresholds per feature in the binned layout
 constexpr int kSplitTiles = 128;  // below this many 256-txn tiles the forest runs the tree-split path
@@ -151,6 +154,14 @@ struct PreBin {
   bool want = false, done = false;
 };
 
+// The sparse image of a forest on the device (forest_sparse.hip): node records, then the two arrays indexed by leaf
+// ordinal. gen: the PackedForest::gen it was built for (0 = none).
+struct SparseImage {
+  DeviceBuffer nodes, leaf_val, leaf_ids;
+  int64_t n_nodes = 0, n_leaves = 0;
+  uint64_t gen = 0;
+};
+
 // A forest repacked into perfect depth-D trees stored as 1-based heaps (see forest.hip header and
 // DESIGN.md "Forest layout"): per tree 2^D node records {f32 thr, u32 meta} (slot 0 unused; children
 // of slot s are 2s / 2s+1) then 2^D leaf values (f32 XGBoost, f64 Isolation Forest); chunks of
@@ -158,6 +169,10 @@ struct PreBin {
 //   meta = feature * kTile * 4 (byte offset of the feature row in the LDS tile) | default_left << 31.
 struct PackedForest {
   bool loaded = false;
+  // kind FD_FOREST_SKLEARN_PROBA or deeper than kMaxDepth: only the sparse image exists (no heap, no binned layout;
+  // chunk / b_chunk / n_chunk are 0 and their buffers are not read), every launch goes to forest_sparse_kernel
+  bool sparse_only = false;
+  mutable SparseImage sp;  // built at load for a sparse-only forest, else on the first launch under option 11
   int kind = 0;
   int n_trees = 0;
   int n_chunks = 0;
@@ -560,6 +575,7 @@ struct Engine {
   hipEvent_t slot_pass_ev = nullptr;
   unsigned long long pipe_iter = 0;
   unsigned long long pipe_iter_total = 0;  // counter "pipelined_batches"
+  unsigned long long sparse_total = 0;        // counter "forest_sparse_launches": launches of forest_sparse_kernel
   unsigned long long ens_single_total = 0;    // counter "ensemble_single_launches": fd_forest_predict batches run by
                                               // the fused kernel over one forest (config 2's timed kernel)
   unsigned long long pipe_split_total = 0;    // counter "pipelined_split_batches": of those, split rows
@@ -655,6 +671,25 @@ struct HostPack {
 // min_depth: pad every tree to at least this depth (the ensemble kernel's common depth)
 HostPack pack_forest_host(const fd_forest_params& p, const fd_tree_arrays& t, int min_depth = 0);
 void repack_forest(PackedForest& pf, const fd_forest_params& p, const fd_tree_arrays& t);
+// sklearn's (double)x <= thr as the engine's f32 "x < t" (forest.hip)
+float sklearn_threshold_to_lt(double thr);
+// forest_sparse.hip: the sparse (pointer) layout for trees of any depth (include/fdengine.h fd_pack_forest_sparse_host)
+struct SparsePack {
+  std::vector<uint32_t> nodes;    // 2 words per node: f32 threshold bits, meta
+  std::vector<char> leaf_val;     // n_leaves values: f32 XGBoost, f64 the sklearn kinds
+  std::vector<int32_t> leaf_ids;  // n_leaves original node ids
+  int kind = 0, n_trees = 0, depth = 0, num_feature = 0, leaf_bytes = 0;
+  int64_t n_nodes = 0, n_leaves = 0;
+  float base_margin = 0.f;
+};
+SparsePack pack_forest_sparse_host(const fd_forest_params& p, const fd_tree_arrays& t);
+// the deepest leaf of a well-formed forest (root = 0), -1 when the arrays are incomplete or not trees
+int forest_depth_probe(const fd_tree_arrays& t);
+// fd_load_forest for a forest that takes the sparse layout only
+void load_forest_sparse(PackedForest& pf, const fd_forest_params& p, const fd_tree_arrays& t);
+// forest_sparse_kernel over the forest on `stream` (the image is built first when the forest has none yet)
+void launch_forest_sparse(Engine& e, const PackedForest& pf, const float* d_X, int64_t n, int32_t ld, double* d_prob,
+                          double* d_raw, int32_t* d_leaf, hipStream_t stream);
 // two forests of a latency batch, one binning launch (forest.hip); false: not applicable, nothing launched
 bool launch_forest_pair(Engine& e, const PackedForest& pa, const PackedForest& pb, const float* d_X, int64_t n,
                         int32_t ld, double* d_prob_a, double* d_prob_b);

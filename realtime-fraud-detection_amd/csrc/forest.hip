@@ -25,6 +25,7 @@
 // path-length sum are reproduced bit for bit.
 // forest_kernel1: 256 threads, thread per transaction (deep trees D = 9..10; A/B reference).
 // Small batches: the tree-split path (split_bin / split_walk / split_sum kernels, below).
+// Trees deeper than kMaxDepth and the sklearn predict_proba kind: the sparse layout, forest_sparse.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -65,6 +66,10 @@ int tree_depth(const int32_t* L, const int32_t* R, int64_t m) {
   return maxd;
 }
 
+size_t round1k(size_t b) { return (b + 1023) / 1024 * 1024; }
+
+}  // namespace
+
 // sklearn compares (double)x_f32 <= thr_f64 (sklearn/tree/_tree.pyx _apply_dense). For an f32 x this
 // is x <= floor32(thr), i.e. x < next_up(floor32(thr)): rewrite it as the engine's single x < t form.
 float sklearn_threshold_to_lt(double thr) {
@@ -72,10 +77,6 @@ float sklearn_threshold_to_lt(double thr) {
   if ((double)f > thr) f = std::nextafter(f, -INFINITY);
   return std::nextafter(f, INFINITY);
 }
-
-size_t round1k(size_t b) { return (b + 1023) / 1024 * 1024; }
-
-}  // namespace
 
 // LDS image of the tile kernels 3, 4 and 6 (one map for the three layouts: the tile holds f32 values or u32 bin words)
 size_t lds_bytes_tile(int nf, size_t chunk_stride, int ch, size_t leaf_sz) {
@@ -279,8 +280,16 @@ void upload(DeviceBuffer& d, const std::vector<T>& h) {
 }  // namespace
 
 void repack_forest(PackedForest& pf, const fd_forest_params& p, const fd_tree_arrays& t) {
+  // the predict_proba kind and forests deeper than the heaps reach: the sparse layout only (forest_sparse.hip);
+  // everything else is packed and dispatched as before
+  if (p.kind == FD_FOREST_SKLEARN_PROBA || forest_depth_probe(t) > kMaxDepth) {
+    load_forest_sparse(pf, p, t);
+    return;
+  }
   const HostPack hp = pack_forest_host(p, t);
   forest_loaded(pf, p, t);
+  pf.sparse_only = false;
+  pf.sp.gen = 0;  // a sparse image of the slot's earlier forest is stale (rebuilt on the next option-11 launch)
   upload(pf.blob, hp.blob);
   upload(pf.leaf_ids, hp.leaf_ids);
   pf.kind = hp.kind;
@@ -1015,7 +1024,10 @@ void launch_split(const PackedForest& pf, const float* d_X, int64_t n, int32_t l
 }
 
 // the tree-split path: for forests with the binned layout; option 6 forces it, auto takes it below kSplitTiles tiles
-bool split_capable(const PackedForest& pf) { return pf.binned && pf.depth <= 8 && pf.b_chunk % 4 == 0; }
+// (a sparse-only forest has no binned layout: the pair paths built on split_path decline it here)
+bool split_capable(const PackedForest& pf) {
+  return !pf.sparse_only && pf.binned && pf.depth <= 8 && pf.b_chunk % 4 == 0;
+}
 bool split_path(const Engine& e, const PackedForest& pf, int64_t n) {
   const int64_t blocks = (n + kTile - 1) / kTile;
   return split_capable(pf) && (e.forest_variant == 6 || (e.forest_variant == 0 && blocks < kSplitTiles));
@@ -1037,7 +1049,8 @@ extern "C" __attribute__((visibility("default"))) int fd_debug_tl_forest(unsigne
 // IsolationForest 38.1 vs 38.7 us, tools/forest_sweep.py), else kernel 4 (binned), else kernel 3
 // (depth <= 8), else kernel 1; 8 forces kernel 6; 1/2/3 force kernel 1/3/4; 6 forces the tree-split
 // small-batch path, which auto also takes below kSplitTiles tiles (FD_ERR_UNSUPPORTED when the forest
-// cannot use it).
+// cannot use it); 11 forces forest_sparse_kernel (forest_sparse.hip), which a sparse-only forest — the
+// predict_proba kind, or trees deeper than kMaxDepth — takes whatever the option says.
 // Two forests of a latency batch on one stream (score_matrix, small_streams 0): one binning launch for both,
 // then each forest's walk and sum. false: not applicable (a forest off the split path); nothing launched.
 bool launch_forest_pair(Engine& e, const PackedForest& pa, const PackedForest& pb, const float* d_X, int64_t n,
@@ -1177,8 +1190,14 @@ void launch_forest(Engine& e, const PackedForest& pf, const float* d_X, int64_t 
   const int64_t blocks = (n + kTile - 1) / kTile;
   FD_REQUIRE(blocks < (1ll << 31), FD_ERR_INVALID_ARG, "batch too large");
   const int v = e.forest_variant;
-  FD_REQUIRE(v == 0 || v == 1 || v == 2 || v == 3 || v == 6 || v == 8, FD_ERR_INVALID_ARG,
-             "forest_kernel option must be 0, 1, 2, 3, 6 or 8");
+  FD_REQUIRE(v == 0 || v == 1 || v == 2 || v == 3 || v == 6 || v == 8 || v == 11, FD_ERR_INVALID_ARG,
+             "forest_kernel option must be 0, 1, 2, 3, 6, 8 or 11");
+
+  // the sparse layout: the only one of a predict_proba or deep forest; option 11 forces it for any forest
+  if (pf.sparse_only || v == 11) {
+    launch_forest_sparse(e, pf, d_X, n, ld, d_prob, d_raw, d_leaf, stream ? stream : e.stream);
+    return;
+  }
 
   // small batches: tree-split latency path (option 6 forces it; auto below 128 tiles)
   if (v == 6)

@@ -74,10 +74,13 @@ __device__ __forceinline__ void stage_chunk_asm(const char* __restrict__ src, ui
 __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // XGBoost common::Sigmoid (src/common/math.h) in f32 / sklearn score -> decision -> the
-// reference's 1/(1+exp(s)) in f64.
+// reference's 1/(1+exp(s)) in f64 / sklearn's forest predict_proba: the summed tree probabilities divided once by
+// the number of trees (if_denom carries it).
 template <int KIND, typename LeafT>
 __device__ __forceinline__ double forest_prob(LeafT acc, double if_offset, double if_denom) {
-  if (KIND == FD_FOREST_XGB_BINARY_LOGISTIC) {
+  if (KIND == FD_FOREST_SKLEARN_PROBA) {
+    return (double)acc / if_denom;
+  } else if (KIND == FD_FOREST_XGB_BINARY_LOGISTIC) {
     const float m = (float)acc;
     const float xm = fminf(-m, 88.7f);
     const float denom = expf(xm) + 1.0f + 1e-16f;

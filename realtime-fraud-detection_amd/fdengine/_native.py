@@ -26,6 +26,7 @@ FD_RESTORE_SKIP_SINK = 2
 
 FD_FOREST_XGB_BINARY_LOGISTIC = 1
 FD_FOREST_SKLEARN_IFOREST = 2
+FD_FOREST_SKLEARN_PROBA = 3
 
 FD_MAX_MODELS = 8
 FD_BLEND_WEIGHTED_AVERAGE = 0
@@ -84,6 +85,19 @@ class fd_pack_info(C.Structure):
         ("layout", C.c_int32),
         ("n_thresholds", C.c_int64),
         ("bin_steps", C.c_int32),
+    ]
+
+
+class fd_sparse_info(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("n_trees", C.c_int32),
+        ("depth", C.c_int32),
+        ("leaf_bytes", C.c_int32),
+        ("n_nodes", C.c_int64),
+        ("n_leaves", C.c_int64),
+        ("base_margin", C.c_float),
+        ("pad", C.c_int32),
     ]
 
 
@@ -306,6 +320,8 @@ SIGNATURES = {
                                       C.POINTER(fd_pack_info)]),
     "fd_pack_forest_binned_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), _vp, _i64,
                                              _vp, _i64, _vp, C.POINTER(fd_pack_info)]),
+    "fd_pack_forest_sparse_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), _vp, _i64,
+                                             _vp, _i64, _vp, _i64, C.POINTER(fd_sparse_info)]),
 }
 
 

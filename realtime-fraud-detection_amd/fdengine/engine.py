@@ -615,6 +615,21 @@ def pack_forest_binned_host(fa: ForestArrays):
     return blob.tobytes(), thr, off, info
 
 
+def pack_forest_sparse_host(fa: ForestArrays):
+    """Host-only sparse repack (no GPU; trees of any depth): -> (nodes uint32 [n_nodes, 2] {f32 threshold bits, meta},
+    leaf values f32 / f64 [n_leaves], leaf ids int32 [n_leaves], fd_sparse_info). Words: include/fdengine.h."""
+    p, t, keep = fa.c_structs()
+    info = N.fd_sparse_info()
+    N.call("fd_pack_forest_sparse_host", C.byref(p), C.byref(t), None, 0, None, 0, None, 0, C.byref(info))
+    nodes = np.empty((info.n_nodes, 2), np.uint32)
+    vals = np.empty(info.n_leaves, np.float32 if info.leaf_bytes == 4 else np.float64)
+    ids = np.empty(info.n_leaves, np.int32)
+    N.call("fd_pack_forest_sparse_host", C.byref(p), C.byref(t), C.c_void_p(nodes.ctypes.data), info.n_nodes,
+           C.c_void_p(vals.ctypes.data), info.n_leaves, C.c_void_p(ids.ctypes.data), info.n_leaves, C.byref(info))
+    del keep
+    return nodes, vals, ids, info
+
+
 def read_xgboost_json_native(path) -> ForestArrays:
     """Host-only: the engine's C++ reader of the XGBoost JSON file (fd_xgboost_json_read), as ForestArrays."""
     p = N.fd_forest_params()

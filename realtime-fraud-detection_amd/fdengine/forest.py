@@ -164,3 +164,41 @@ def iforest_from_sklearn(model) -> ForestArrays:
 def load_isolation_forest_joblib(path: str) -> ForestArrays:
     import joblib
     return iforest_from_sklearn(joblib.load(path))
+
+
+# ------------------------------------------------------------------------- sklearn forest classifiers
+
+_CLASSIFIERS = ("RandomForestClassifier", "ExtraTreesClassifier", "DecisionTreeClassifier")
+
+
+def forest_from_sklearn_classifier(model) -> ForestArrays:
+    """Flatten a fitted sklearn RandomForestClassifier / ExtraTreesClassifier / DecisionTreeClassifier (one tree)
+    with two classes and one output: the models whose predict_proba is the mean of the trees' leaf class fractions
+    (sklearn/ensemble/_forest.py predict_proba: the trees' probabilities summed, divided once by n_estimators).
+    The leaf value is tree_.value[node, 0, 1], column 1 of classes_: what the reference's
+    predict_proba(X)[:, 1] takes (ml/models/model_manager.py:338-346). Anything else (GradientBoosting, whose
+    probability is not a leaf mean; more classes; several outputs) raises UnsupportedModel."""
+    name = type(model).__name__
+    if name not in _CLASSIFIERS:
+        raise UnsupportedModel(f"sklearn model {name} is not on the engine path")
+    if int(getattr(model, "n_outputs_", 1)) != 1:
+        raise UnsupportedModel(f"{name} with {model.n_outputs_} outputs is not supported (one output only)")
+    if len(model.classes_) != 2:
+        raise UnsupportedModel(f"{name} with {len(model.classes_)} classes is not supported (two classes only)")
+    estimators = [model] if name == "DecisionTreeClassifier" else list(model.estimators_)
+    trees = []
+    for est in estimators:
+        t = est.tree_
+        left = np.asarray(t.children_left, dtype=np.int64)
+        leaf = left == -1
+        value = np.asarray(t.value, dtype=np.float64)
+        if value.shape[1:] != (1, 2):  # a tree of a 2-class forest that saw one class still has two columns
+            raise UnsupportedModel(f"{name}: tree value shape {value.shape} is not [nodes, 1, 2]")
+        dl = getattr(t, "missing_go_to_left", None)
+        dl = np.zeros(len(left), np.uint8) if dl is None else np.asarray(dl, dtype=np.uint8)
+        trees.append(dict(left=np.where(leaf, -1, left), right=np.asarray(t.children_right, dtype=np.int64),
+                          feature=np.where(leaf, 0, np.asarray(t.feature, dtype=np.int64)),
+                          threshold=np.where(leaf, 0.0, np.asarray(t.threshold, dtype=np.float64)),
+                          default_left=dl, leaf_value=np.where(leaf, value[:, 0, 1], 0.0)))
+    return _concat(trees, N.FD_FOREST_SKLEARN_PROBA, int(model.n_features_in_),
+                   meta={"n_trees": len(trees), "class": name})

@@ -7,8 +7,12 @@ Same public surface — `load_all_models`, `predict(model_name, features) -> np.
 
   model_type "xgboost"  unchanged XGBoost JSON (`_load_xgboost_model` :157-161) -> engine slot;
                         predict returns predict_proba(X)[:, 1] as float32 (`_predict_xgboost` :309-311)
-  model_type "sklearn"  unchanged joblib IsolationForest (`_load_sklearn_model` :197-200) -> engine
-                        slot; predict returns 1/(1+exp(decision_function)) (`_predict_sklearn` :338-346)
+  model_type "sklearn"  unchanged joblib model (`_load_sklearn_model` :197-200) -> engine slot, by estimator, as
+                        `_predict_sklearn` (:338-346) branches on predict_proba:
+                        RandomForestClassifier / ExtraTreesClassifier / DecisionTreeClassifier (two classes):
+                        predict returns predict_proba(X)[:, 1] (trees of any depth: the engine's sparse layout);
+                        IsolationForest (no predict_proba): predict returns 1/(1+exp(decision_function));
+                        any other estimator is refused at load (logged, model not loaded)
 
   model_type "tensorflow" lstm_sequential weights (`_load_tensorflow_model` :162-165) -> the engine's LSTM
                         head (fdengine/lstm.py formats; the .h5 path's .safetensors/.npz sibling);
@@ -34,7 +38,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 
 from .engine import FraudEngine
-from .forest import UnsupportedModel, iforest_from_sklearn
+from .forest import UnsupportedModel, forest_from_sklearn_classifier, iforest_from_sklearn
 
 log = logging.getLogger("fdengine.model_manager")
 
@@ -81,8 +85,10 @@ def _lstm_weight_file(path: str) -> Optional[str]:
 class EngineForest:
     """A forest resident in the engine (one slot)."""
 
-    def __init__(self, slot: int, kind: str, num_feature: int, n_trees: int, depth: int):
+    def __init__(self, slot: int, kind: str, num_feature: int, n_trees: int, depth: int,
+                 model_class: Optional[str] = None):
         self.slot, self.kind, self.num_feature, self.n_trees, self.depth = slot, kind, num_feature, n_trees, depth
+        self.model_class = model_class  # the estimator's class name (sklearn's error messages name it)
 
 
 def _default_device() -> int:
@@ -151,9 +157,11 @@ class ModelManager:
         if cfg.model_type == "sklearn":
             import joblib
             model = joblib.load(cfg.model_path)
-            if type(model).__name__ != "IsolationForest":
-                raise UnsupportedModel(f"sklearn model {type(model).__name__} is not on the engine path")
-            return self._upload(slot, iforest_from_sklearn(model), "isolation_forest")
+            cls = type(model).__name__
+            if cls == "IsolationForest":  # no predict_proba: the reference's decision_function branch
+                return self._upload(slot, iforest_from_sklearn(model), "isolation_forest", cls)
+            # the predict_proba branch: the forest classifiers (anything else raises UnsupportedModel, by class name)
+            return self._upload(slot, forest_from_sklearn_classifier(model), "sklearn_classifier", cls)
         raise UnsupportedModel(f"model_type {cfg.model_type!r} files are not served by the engine")
 
     def _load_lstm(self, path: str) -> EngineLstm:
@@ -162,10 +170,10 @@ class ModelManager:
         self.engine.load_lstm(w)
         return EngineLstm(w.input_size, w.hidden, w.n_out, path)
 
-    def _upload(self, slot: int, fa, kind: str) -> EngineForest:
+    def _upload(self, slot: int, fa, kind: str, model_class: Optional[str] = None) -> EngineForest:
         self.engine.load_forest(slot, fa)
         info = self.engine.forest_info(slot)
-        return EngineForest(slot, kind, info["num_feature"], info["n_trees"], info["depth"])
+        return EngineForest(slot, kind, info["num_feature"], info["n_trees"], info["depth"], model_class)
 
     # ----------------------------------------------------------------------------- predict
     async def predict(self, model_name: str, features: np.ndarray) -> np.ndarray:
@@ -197,8 +205,8 @@ class ModelManager:
                     raise ValueError(f"Feature shape mismatch, expected: {model.num_feature}, got {X.shape[1]}")
                 return self.engine.predict(model.slot, X).astype(np.float32)
             if X.shape[1] != model.num_feature:  # sklearn's validate_data(reset=False) n_features_in_ check
-                raise ValueError(f"X has {X.shape[1]} features, but IsolationForest is expecting "
-                                 f"{model.num_feature} features as input.")
+                raise ValueError(f"X has {X.shape[1]} features, but {model.model_class or 'IsolationForest'} is "
+                                 f"expecting {model.num_feature} features as input.")
             return self.engine.predict(model.slot, X)
         # reference branches for the DummyModel stand-ins (model_manager.py:288-300, 313-336)
         if model_type == "xgboost":

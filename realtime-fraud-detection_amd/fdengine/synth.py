@@ -209,6 +209,27 @@ def isolation_forest(X_train: np.ndarray, n_estimators: int = 100, contamination
     return m
 
 
+def fraud_labels(X: np.ndarray, seed: int = 11, noise: float = 0.15) -> np.ndarray:
+    """0 / 1 labels for feature_matrix rows: a noisy rule over a few columns, so a forest classifier trained on
+    them grows deep, unbalanced trees (NaN counts as 0)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    Z = np.nan_to_num(np.asarray(X, np.float64))
+    s = 0.6 * Z[:, 1 % Z.shape[1]] + 2.0 * Z[:, 3 % Z.shape[1]] + 0.8 * Z[:, 2 % Z.shape[1]] - 0.05 * Z[:, 0]
+    y = s > np.quantile(s, 0.8)
+    return (y ^ (rng.random(len(y)) < noise)).astype(np.int64)
+
+
+def random_forest(X_train: np.ndarray, y_train: Optional[np.ndarray] = None, n_estimators: int = 100,
+                  random_state: int = 42, extra: bool = False, **kw):
+    """A fitted RandomForestClassifier (extra: ExtraTreesClassifier) on fraud_labels, sklearn's defaults otherwise:
+    unbounded depth. n_jobs is left alone (predict_proba's summation order depends on it)."""
+    from sklearn.ensemble import ExtraTreesClassifier, RandomForestClassifier
+    cls = ExtraTreesClassifier if extra else RandomForestClassifier
+    m = cls(n_estimators=n_estimators, random_state=random_state, **kw)
+    m.fit(X_train, fraud_labels(X_train) if y_train is None else y_train)
+    return m
+
+
 # ------------------------------------------------------------------ hash-derived card populations
 # For the sharded configurations (BASELINE config 4: 100M cards over 8 GPUs) every rank needs the
 # attributes of the cards it owns and of the cards its own stream touches, without materialising the
