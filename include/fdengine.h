@@ -632,7 +632,8 @@ int fd_state_restore(fd_engine* eng, const char* path, int32_t shard, int32_t n_
    merchant = index of merchant_id in fd_ingest_set_merchants (-1 unknown / null); payment_method /
    transaction_type / card_type = index in fd_ingest_set_vocab (255 null, FD_VOCAB_OTHER unknown);
    ip_class 0 null / 1 private / 2 public and user_agent_flag 0 / 1 / 255 null (FeatureExtractor.java:434-451);
-   ts_ms = ISO-8601 timestamp as epoch ms (UTC without offset); amount_cents exact. Declared semantics and
+   ts_ms = ISO-8601 timestamp as epoch ms (UTC without offset); amount_cents exact. A number counts by its first
+   19 significant digits; strings and keys are decoded (JSON escapes) before they are read. Declared semantics and
    limits: DESIGN.md "Ingest". Rows with status & FD_INGEST_INVALID are the reference's ERROR placeholder
    (all other columns default). Any output pointer may be NULL. */
 #define FD_VOCAB_OTHER 254
@@ -641,7 +642,8 @@ enum fd_ingest_status {
   FD_INGEST_MALFORMED = 1,     /* not one JSON object / bad member syntax / value of the wrong type */
   FD_INGEST_TOO_LONG = 2,      /* message longer than 4080 bytes */
   FD_INGEST_UNKNOWN_VOCAB = 4, /* a payment / type / card string outside its vocabulary (code FD_VOCAB_OTHER) */
-  FD_INGEST_INEXACT = 8,       /* sub-cent amount (rounded half-even) or a > 19-digit number at a rounding tie */
+  FD_INGEST_INEXACT = 8,       /* sub-cent amount (rounded half-even), an amount with a non-zero digit beyond the
+                                  19th, or a double whose digits beyond the 19th could change its rounding */
   FD_INGEST_MISSING = 16,      /* user_id, amount or timestamp missing / null */
 };
 #define FD_INGEST_INVALID (FD_INGEST_MALFORMED | FD_INGEST_TOO_LONG | FD_INGEST_MISSING)

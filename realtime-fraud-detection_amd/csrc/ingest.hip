@@ -251,6 +251,83 @@ __device__ __forceinline__ int scan_string(const Reader& s, int pos, int end, S&
   return -1;
 }
 
+// decode the content s[a..b) of a string that scan_string / skip_string accepted, in place over its raw bytes in the
+// stage (the decoded text is never longer); returns the decoded end. Only where the text must be ASCII to mean
+// anything (a number, an instant): a character that neither holds — non-ASCII, a control character, '"' or '\\' —
+// becomes the single byte 0xFF. The rare path (the simulator escapes nothing there): a plain byte loop.
+__device__ __forceinline__ int unescape_in_place(const Reader& s, int a, int b) {
+  unsigned char* st = const_cast<unsigned char*>(s.st) + s.shift;
+  int o = a;
+  for (int i = a; i < b;) {
+    int c = st[i++];
+    if (c == '\\') {
+      c = st[i++];
+      if (c == 'u') {
+        int v = 0;
+        for (int k = 0; k < 4; ++k) v = v * 16 + hexval(st[i + k]);
+        i += 4;
+        c = (v >= 0x20 && v < 0x80 && v != '"' && v != '\\') ? v : 0xFF;
+      } else {
+        c = c == '/' ? c : 0xFF;  // the others decode to a control character, '"' or '\\'
+      }
+    }
+    st[o++] = (unsigned char)c;
+  }
+  return o;
+}
+
+// every string spelled with escapes in the object or array at s[pos] (brackets balanced up to `end`: the structure
+// phase saw to that) rewritten in place as the plain spelling of its decoded text: "l\u0061t" -> "lat" and spaces up to
+// where it ended, which JSON allows after any key or value. A character that no plain spelling holds (and no number
+// or "lat" / "lon" either) becomes 0xFF; an invalid escape leaves a control byte in the string, so that the walk which
+// follows rejects it as it would have. One pass, a byte at a time: only locations off the simulator's shape get here.
+__device__ __forceinline__ void plain_strings_in_place(const Reader& s, int pos, int end) {
+  unsigned char* st = const_cast<unsigned char*>(s.st) + s.shift;
+  int depth = 0, o = 0;
+  bool in = false, esc = false;
+  for (int i = pos; i < end; ++i) {
+    int c = st[i];
+    if (!in) {
+      if (c == '"') {
+        in = true;
+        esc = false;
+        o = i + 1;
+      } else if ((c | 0x20) == '{') {  // '[' | 0x20 == '{'
+        ++depth;
+      } else if ((c | 0x20) == '}' && --depth == 0) {
+        return;
+      }
+      continue;
+    }
+    if (c == '"') {
+      if (esc) {
+        st[o] = '"';
+        while (++o <= i) st[o] = ' ';
+      }
+      in = false;
+      continue;
+    }
+    if (c == '\\') {
+      esc = true;
+      c = st[++i];
+      if (c == 'u') {
+        int v = 0;
+        for (int k = 1; k <= 4; ++k) v = v < 0 ? v : (hexval(st[i + k]) < 0 ? -1 : v * 16 + hexval(st[i + k]));
+        i += 4;
+        c = (v >= 0x20 && v < 0x80 && v != '"' && v != '\\') ? v : (v < 0 ? 1 : 0xFF);
+      } else {
+        c = c == '/' ? c : (c == '"' || c == '\\' || c == 'b' || c == 'f' || c == 'n' || c == 'r' || c == 't') ? 0xFF : 1;
+      }
+      if (c == 1) {
+        st[o] = 1;
+        return;
+      }
+    }
+    if (esc) st[o] = (unsigned char)c;
+    ++o;
+  }
+}
+
 // a run of decimal digits from s[i] (at least i < end), four bytes per LDS access: per-byte digit test on the
 // dword (t = byte ^ '0' is a digit iff its high nibble is 0 and its low nibble + 6 stays below 16), the digits
 // before the first other byte fed to `digit` in order; returns the index after the run
@@ -507,6 +584,7 @@ __device__ __forceinline__ int scan_latlon(const Reader& s, int pos, int end, De
   // ','), recognised by dword compares; any other shape -> the general walk below from the start
   if (pos + 8 <= end && s.word(pos) == 0x616C227Bu && s.word(pos + 4) == 0x203A2274u) {  // {"la  t":_
     int i = pos + 8;
+    Decimal first;  // d0 / d1 are written on success only: nothing of a failed attempt stays live below
     for (int t = 0; t < 2; ++t) {  // one number-scan site for both coordinates
       const bool q = s[i] == '"';
       Decimal tmp;
@@ -514,12 +592,13 @@ __device__ __forceinline__ int scan_latlon(const Reader& s, int pos, int end, De
       if (e >= 0 && q) e = (e < end && s[e] == '"') ? e + 1 : -1;
       if (e < 0) break;
       if (t == 0) {
-        d0 = tmp;
+        first = tmp;
         if (!(e + 9 <= end && s.word(e) == 0x6C22202Cu && s.word(e + 4) == 0x3A226E6Fu && s[e + 8] == ' ')) break;
         i = e + 9;  // ,_"l  on":  _
       } else {
-        d1 = tmp;
         if (e >= end || s[e] != '}') break;
+        d0 = first;
+        d1 = tmp;
         has0 = has1 = 1;
         return e + 1;
       }
@@ -528,6 +607,7 @@ __device__ __forceinline__ int scan_latlon(const Reader& s, int pos, int end, De
   has0 = has1 = 0;
   if (lit_at(s, pos, end, "null", 4)) return pos + 4;
   if (s[pos] != '{') return -1;
+  plain_strings_in_place(s, pos, end);  // Jackson decodes keys and numeric strings before it reads them
   int i = pos + 1;
   while (i < end && is_ws(s[i])) ++i;
   if (i < end && s[i] == '}') return i + 1;
@@ -536,7 +616,7 @@ __device__ __forceinline__ int scan_latlon(const Reader& s, int pos, int end, De
     const int ks = i;
     i = skip_string(s, i, end);
     if (i < 0) return -1;
-    // "lat" / "lon" (unescaped spelling)
+    // "lat" / "lon" (plain_strings_in_place has decoded an escaped spelling)
     const int t = (i - ks == 5 && s[ks + 1] == 'l' && ((s[ks + 2] == 'a' && s[ks + 3] == 't') ||
                                                          (s[ks + 2] == 'o' && s[ks + 3] == 'n')))
                       ? (s[ks + 2] == 'a' ? 0 : 1)
@@ -921,10 +1001,10 @@ __global__ void __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_e
     } else if (ch == '"') {
       e = scan_string(s, v, L, st);
       kind = 1;
-      if (e >= 0 && (f == F_AMOUNT || f == F_SCORE || f == F_HOUR)) {  // numeric string
-        if (st.escaped) e = -1;
-        num_a = v + 1;
-        num_b = e - 1;
+      if (e >= 0 && (f == F_AMOUNT || f == F_SCORE || f == F_HOUR || f == F_TIMESTAMP)) {
+        // a numeric string or an instant: its text is s[v + 1 .. num_b), decoded first if it was escaped (Jackson)
+        num_b = st.escaped ? unescape_in_place(s, v + 1, e - 1) : e - 1;
+        if (f != F_TIMESTAMP) num_a = v + 1;
       }
     } else if (lit_at(s, v, L, "null", 4)) {
       e = v + 4;
@@ -1009,7 +1089,7 @@ __global__ void __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_e
       case F_TIMESTAMP: {
         if (kind == 0) break;
         int64_t ms;
-        if (kind != 1 || st.escaped || !parse_iso_w(s, v + 1, e - 1, &ms)) {
+        if (kind != 1 || !parse_iso_w(s, v + 1, num_b, &ms)) {
           bad = true;
           break;
         }
@@ -1019,9 +1099,9 @@ __global__ void __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_e
       case F_WEEKEND: case F_FRAUD: {
         if (kind == 3 || kind == 4) {
           val.u = kind == 3 ? 1 : 0;
-        } else if (kind == 1 && !st.escaped && st.nbytes == 4 && st.head == 0x65757274ull) {  // "true"
+        } else if (kind == 1 && st.nbytes == 4 && st.head == 0x65757274ull) {  // "true" (decoded)
           val.u = 1;
-        } else if (kind == 1 && !st.escaped && st.nbytes == 5 && st.head == 0x65736C6166ull) {  // "false"
+        } else if (kind == 1 && st.nbytes == 5 && st.head == 0x65736C6166ull) {  // "false"
           val.u = 0;
         } else if (kind == 2 && !dec0.frac_or_exp) {  // integer coercion: 0 -> false, other -> true
           val.u = dec0.w != 0 ? 1 : 0;
