@@ -375,6 +375,44 @@ int fd_lstm_predict_host(fd_engine* eng, const float* seq, int64_t n, int32_t T,
 int fd_features_seq_device(fd_engine* eng, const fd_txn_batch* txns, int64_t n, float* d_vectors, double* d_raw,
                            float* d_seq);
 
+/* ---------------------------------------------------------------- PyTorch MLP head (graph_neural) */
+/* Replaces _create_pytorch_model_architecture (ml/models/model_manager.py:202-242) for the registry's
+   model_type "pytorch" entry graph_neural: n_layers nn.Linear layers (defaults 64 -> 64 -> 64 -> 2), ReLU after
+   every layer but the last (torch.relu: a NaN stays a NaN), dropout the identity in eval(), softmax(dim=1).
+   Weights in PyTorch layout, f32: layer i's weight [dims[i+1] x dims[i]] row-major (nn.Linear.weight), its bias
+   [dims[i+1]] or NULL (zeros). Non-finite weights are accepted and computed. Computed in f32 on the matrix cores.
+   Limits (FD_ERR_UNSUPPORTED, named in the message): n_layers in [2, 8]; in_dim = dims[0] in [1, 64]; every hidden
+   width in [1, 64]; dims[n_layers] == 2 (the reference always builds output_dim = 2). FD_ERR_INVALID_ARG: a NULL
+   weight, a nonzero dims entry beyond dims[n_layers]. */
+typedef struct {
+  int32_t n_layers;                 /* Linear layers, 2..8 */
+  int32_t dims[9];                  /* dims[0] = in_dim, dims[i+1] = layer i's outputs; dims[n_layers] == 2 */
+  const float* weight[8];           /* layer i: [dims[i+1] x dims[i]] row-major (PyTorch nn.Linear.weight) */
+  const float* bias[8];             /* layer i: [dims[i+1]] or NULL */
+} fd_mlp_params;
+/* Replaces _load_pytorch_model (ml/models/model_manager.py:168-179: torch.load + load_state_dict). One MLP per
+   engine; a load replaces the previous one. Validates and packs with fd_pack_mlp_host. */
+int fd_load_mlp(fd_engine* eng, const fd_mlp_params* params);
+/* The reference drops a model by deleting its registry entry (reload_model, :348-369; cleanup, :405-414); idempotent. */
+int fd_unload_mlp(fd_engine* eng);
+/* The loaded model's shape (get_model_info's metadata, :393-399): layer count, dims[0], dims[1]; any may be NULL.
+   FD_ERR_NOT_LOADED without a model. */
+int fd_mlp_info(fd_engine* eng, int32_t* n_layers, int32_t* in_dim, int32_t* hidden);
+/* Replaces _predict_pytorch (ml/models/model_manager.py:321-330): d_prob[i] = softmax(model(X[i]))[1], the f32
+   value widened to f64. X: n rows of ld-strided f32, ld >= in_dim (FD_ERR_INVALID_ARG otherwise); columns >= in_dim
+   are never read. FD_ERR_NOT_LOADED without a model; n == 0 does nothing. */
+int fd_mlp_predict_device(fd_engine* eng, const float* d_X, int64_t n, int32_t ld, double* d_prob);
+int fd_mlp_predict_host(fd_engine* eng, const float* X, int64_t n, int32_t ld, double* prob);
+/* Every load-time check and the packing of fd_load_mlp, without a device (_create_pytorch_model_architecture's
+   shape rules, :202-242): writes the packed model (header, then per layer the weights in the kernel's operand order
+   and the padded bias) to blob when it is not NULL (FD_ERR_INVALID_ARG when cap is too small) and its size to
+   *bytes. */
+int fd_pack_mlp_host(const fd_mlp_params* params, void* blob, int64_t cap, int64_t* bytes);
+/* In the scoring calls (fd_score_matrix_*, fd_score_batch_*, fd_score_records_*, fd_sharded_step) a model whose
+   slot is FD_SLOT_MLP is the MLP over the batch's scoring vectors (the ensemble's graph_neural member,
+   ml/models/ensemble_predictor.py's per-model predict over the same features). */
+#define FD_SLOT_MLP 65
+
 /* ---------------------------------------------------------------- batched scoring */
 /* Replaces the per-transaction loop of /batch-predict (ml/main.py:235-249) for prepared scoring
    vectors: every forest model scores the same X, then the blend runs, all on the device.
@@ -695,7 +733,8 @@ int fd_ingest_scalar_host(int32_t kind, const uint8_t* text, int32_t n, double* 
 enum fd_timing_kind { FD_TIMING_ALL = -1, FD_TIMING_XGB = 0, FD_TIMING_IFOREST = 1, FD_TIMING_FEATURES = 2,
                       FD_TIMING_BLEND = 3, FD_TIMING_ROUTE = 4, FD_TIMING_LSTM = 5,
                       FD_TIMING_WINDOWS = 6, FD_TIMING_INGEST = 7,
-                      FD_TIMING_ENSEMBLE = 8 /* fused XGBoost + IsolationForest + blend kernel */ };
+                      FD_TIMING_ENSEMBLE = 8 /* fused XGBoost + IsolationForest + blend kernel */,
+                      FD_TIMING_MLP = 9 /* the MLP head's kernel (fd_mlp_predict_*, FD_SLOT_MLP) */ };
 int fd_engine_set_timing(fd_engine* eng, int enable);
 /* Engine tuning knobs (for A/B measurement; defaults are the tuned choices):
      "forest_kernel": 0 auto, 1 force the 256-thread kernel, 2 force the 1024-thread tree-split kernel
@@ -711,6 +750,10 @@ int fd_engine_set_timing(fd_engine* eng, int enable);
      communicators (fd_comm_init), else wide; 1 wide (24 XGBoost / 16 IsolationForest trees per chunk, 148 KB of
      LDS); 2 compact (20 / 12, 132 KB: room for an RCCL kernel on the same CU). Outputs are identical.
      "lstm_rows": LSTM tile, 0 auto (4 transactions below 4096, else 16), 4 or 16
+     "mlp_form": the MLP head's kernel for the reference shape (3 layers, padded widths 64): 0 (default) weights in
+     registers, 1 the LDS form every other shape takes
+     "mlp_wgs_per_cu": the MLP head's persistent grid, workgroups per CU: 0 (default) two where they fit, else 1..8
+     (capped by what fits)
      "timing_every": N >= 1, fd_engine_set_timing records HIP events on one launch in N of each timing kind
      (the others run without event records; fd_timing_read's launch count is the timed ones)
      "small_streams": latency batches (< 32768 transactions) with the LSTM head and / or several forests: 0
@@ -753,6 +796,7 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    fd_score_records_pipelined so far), "pipelined_compact_batches" (of those, scored by the fused ensemble kernel from
    the compact 64-B rows: no vectors requested), "ensemble_single_launches" (fd_forest_predict batches scored by the
    fused kernel over one forest), "forest_sparse_launches" (launches of the sparse-layout forest kernel),
+   "mlp_launches" (launches of the MLP head's kernel),
    "pipelined_slot_stream_batches" (of those, with the slot pass on
    its own stream), "pipelined_host_ns" (host nanoseconds inside fd_score_batch_pipelined), "sharded_steps" (fd_sharded_step calls), "rccl_ops" (RCCL operations the exchanges issued: sends, receives,
    all-gathers) and "sharded_host_ns_<phase>" (host

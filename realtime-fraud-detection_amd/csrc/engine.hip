@@ -95,7 +95,8 @@ static fd::PackedForest& slot_of(Engine& e, int slot) {
 
 // Score the same feature matrix with every forest model, then blend (all on e.stream). A model in slot
 // FD_SLOT_LSTM runs the LSTM head over d_seq (n x T x 16) on the auxiliary stream, forked after
-// everything already queued on e.stream (the feature kernel that wrote d_seq) and joined before the blend.
+// everything already queued on e.stream (the feature kernel that wrote d_seq) and joined before the blend. A model in
+// slot FD_SLOT_MLP is the MLP head over dX (mlp.hip), on e.stream beside the forests.
 // Returns true when the route result records were written too (the fused ensemble kernel writes them in its
 // epilogue); otherwise the caller packs them from the columns.
 static bool score_matrix(Engine& e, const fd_blend_params& p, const int32_t* slots, const double* const* ext,
@@ -123,7 +124,8 @@ static bool score_matrix(Engine& e, const fd_blend_params& p, const int32_t* slo
   // 1 the LSTM and every forest after the first on aux; 2 the LSTM on aux, the other forests on aux2 (forked
   // after everything queued so far, i.e. the feature kernel). Large batches: the LSTM on aux.
   int n_forests = 0;
-  for (int m = 0; m < M; ++m) n_forests += (!(present && !present[m]) && slots[m] >= 0 && slots[m] != FD_SLOT_LSTM);
+  auto is_forest = [&](int m) { return slots[m] >= 0 && slots[m] != FD_SLOT_LSTM && slots[m] != FD_SLOT_MLP; };
+  for (int m = 0; m < M; ++m) n_forests += (!(present && !present[m]) && is_forest(m));
   const bool latency = (n + fd::kTile - 1) / fd::kTile < fd::kSplitTiles;
   const int ss = latency ? e.small_streams : 2;
   const bool small = latency && n_forests > 1;
@@ -193,7 +195,7 @@ static bool score_matrix(Engine& e, const fd_blend_params& p, const int32_t* slo
   if (small && n_forests == 2 && (ss == 0 || (e.latency_fused && !use2))) {
     int fm[2], k = 0;
     for (int m = 0; m < M && k < 2; ++m)
-      if (!(present && !present[m]) && slots[m] >= 0 && slots[m] != FD_SLOT_LSTM) fm[k++] = m;
+      if (!(present && !present[m]) && is_forest(m)) fm[k++] = m;
     const fd::PackedForest& pa = slot_of(e, slots[fm[0]]);
     const fd::PackedForest& pb = slot_of(e, slots[fm[1]]);
     if (pa.loaded && pb.loaded) {
@@ -233,9 +235,12 @@ static bool score_matrix(Engine& e, const fd_blend_params& p, const int32_t* slo
   int forests_seen = 0;
   for (int m = 0; m < M; ++m) {
     if ((present && !present[m]) || slots[m] == FD_SLOT_LSTM) continue;
-    if (paired && slots[m] >= 0) continue;
+    if (paired && is_forest(m)) continue;
     double* col = dMP + (size_t)m * n;
-    if (slots[m] >= 0) {
+    if (slots[m] == FD_SLOT_MLP) {
+      fd::launch_mlp(e, e.stream, dX, n, ld, col);
+      cols[m] = col;
+    } else if (slots[m] >= 0) {
       const fd::PackedForest& pf = slot_of(e, slots[m]);
       FD_REQUIRE(pf.loaded, FD_ERR_NOT_LOADED, "Model in slot " + std::to_string(slots[m]) + " not loaded");
       const bool side = small && forests_seen++ > 0;
@@ -345,7 +350,7 @@ int fd_engine_destroy(fd_engine* eng) {
   fd::windows_release(e);
   fd::sink_release(e);
   for (auto* b : {&e.route_blk, &e.route_blk_stream, &e.route_out, &e.route_err, &e.seq_buf, &e.seq_desc, &e.lstm.wpk, &e.lstm.wpk4, &e.lstm.bias,
-                  &e.lstm.wout, &e.lstm.bout, &e.state.seq})
+                  &e.lstm.wout, &e.lstm.bout, &e.state.seq, &e.mlp.blob})
     b->release();
   if (e.aux_stream) {
     (void)hipStreamSynchronize(e.aux_stream);
@@ -483,6 +488,8 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
   } else if (k == "forest_sparse_launches") {  // launches of forest_sparse_kernel: predict_proba forests, forests
     // deeper than 10 levels, and any forest under option forest_kernel = 11
     *value = (int64_t)e.sparse_total;
+  } else if (k == "mlp_launches") {  // launches of the MLP head's kernel (fd_mlp_predict_*, FD_SLOT_MLP models)
+    *value = (int64_t)e.mlp_total;
   } else if (k == "latency_prebinned_batches") {  // latency pair launches that used the feature kernel's bins
     *value = (int64_t)e.prebin_total;
   } else if (k == "pipelined_split_batches") {  // of the compact ones: split rows (compact_vectors 2)
@@ -644,6 +651,12 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value) {
   } else if (k == "lstm_rows") {  // LSTM tile: 0 auto (4 below 4096 transactions, else 16), 4 or 16
     FD_REQUIRE(value == 0 || value == 4 || value == 16, FD_ERR_INVALID_ARG, "lstm_rows must be 0, 4 or 16");
     e.lstm_rows = (int)value;
+  } else if (k == "mlp_form") {  // MLP head: 0 auto (the reference shape's register form), 1 the LDS form always
+    FD_REQUIRE(value == 0 || value == 1, FD_ERR_INVALID_ARG, "mlp_form must be 0 or 1");
+    e.mlp_form = (int)value;
+  } else if (k == "mlp_wgs_per_cu") {  // MLP head's persistent grid: workgroups per CU, 0 auto (2 where they fit)
+    FD_REQUIRE(value >= 0 && value <= 8, FD_ERR_INVALID_ARG, "mlp_wgs_per_cu must be in 0..8");
+    e.mlp_wgs_per_cu = (int)value;
   } else if (k == "ingest_stop_after") {  // diagnostics: 0 full; 1 stage; 2 + structure; 3 + members
     FD_REQUIRE(value >= 0 && value <= 3, FD_ERR_INVALID_ARG, "ingest_stop_after must be in 0..3");
     e.ingest.stop_after = (int)value;
@@ -1324,7 +1337,7 @@ int fd_score_records_pipelined(fd_engine* eng, const fd_blend_params* params, co
   FD_REQUIRE(params->n_models >= 1 && params->n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, "bad n_models");
   for (int m = 0; m < params->n_models; ++m)
     FD_REQUIRE(slots[m] >= 0 || (present && !present[m]), FD_ERR_INVALID_ARG,
-               "routed scoring needs every present model in a forest slot or FD_SLOT_LSTM");
+               "routed scoring needs every present model in a forest slot, FD_SLOT_LSTM or FD_SLOT_MLP");
   if (n == 0) return FD_OK;
   FD_REQUIRE(d_records != nullptr && d_results != nullptr, FD_ERR_INVALID_ARG, "null records / results");
   pipe_step(e, params, slots, nullptr, present, nullptr, d_records, n, nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -1385,7 +1398,7 @@ int fd_sharded_step(fd_engine* eng, const fd_blend_params* params, const int32_t
   FD_REQUIRE(params->n_models >= 1 && params->n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, "bad n_models");
   for (int m = 0; m < params->n_models; ++m)
     FD_REQUIRE(slots[m] >= 0 || (present && !present[m]), FD_ERR_INVALID_ARG,
-               "routed scoring needs every present model in a forest slot or FD_SLOT_LSTM");
+               "routed scoring needs every present model in a forest slot, FD_SLOT_LSTM or FD_SLOT_MLP");
   FD_REQUIRE(n == 0 || d_fraud_prob, FD_ERR_INVALID_ARG, "null fraud_prob output");
   // the prefetched batch is named by its id: batch_id 0 drops a pending prefetch (on every rank alike: its count
   // exchange completes, its records are never sent); any other id must be the pending one
@@ -1847,6 +1860,84 @@ int fd_lstm_predict_host(fd_engine* eng, const float* seq, int64_t n, int32_t T,
   FD_API_END
 }
 
+int fd_pack_mlp_host(const fd_mlp_params* params, void* blob, int64_t cap, int64_t* bytes) {
+  FD_API_BEGIN
+  FD_REQUIRE(params && bytes, FD_ERR_INVALID_ARG, "null params/bytes");
+  const std::vector<uint32_t> pk = fd::pack_mlp_host(*params);
+  *bytes = (int64_t)pk.size() * 4;
+  if (blob) {
+    FD_REQUIRE(cap >= *bytes, FD_ERR_INVALID_ARG, "blob buffer too small");
+    std::memcpy(blob, pk.data(), pk.size() * 4);
+  }
+  FD_API_END
+}
+
+// every stream a scoring call may have put the MLP's launches on
+static void mlp_quiesce(Engine& e) {
+  FD_HIP(hipStreamSynchronize(e.stream));
+  for (hipStream_t st : e.pipe_stream)
+    if (st) FD_HIP(hipStreamSynchronize(st));
+}
+
+int fd_load_mlp(fd_engine* eng, const fd_mlp_params* params) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "null params");
+  mlp_quiesce(e);  // a reload must not race an in-flight predict
+  fd::load_mlp(e, *params);
+  FD_API_END
+}
+
+int fd_unload_mlp(fd_engine* eng) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  mlp_quiesce(e);
+  e.mlp.blob.release();
+  e.mlp.loaded = false;
+  FD_API_END
+}
+
+int fd_mlp_info(fd_engine* eng, int32_t* n_layers, int32_t* in_dim, int32_t* hidden) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E_quiet(eng);
+  FD_REQUIRE(e.mlp.loaded, FD_ERR_NOT_LOADED, "Model graph_neural (MLP) not loaded");
+  if (n_layers) *n_layers = e.mlp.n_layers;
+  if (in_dim) *in_dim = e.mlp.dims[0];
+  if (hidden) *hidden = e.mlp.dims[1];
+  FD_API_END
+}
+
+int fd_mlp_predict_device(fd_engine* eng, const float* d_X, int64_t n, int32_t ld, double* d_prob) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  fd::launch_mlp(e, e.stream, d_X, n, ld, d_prob);
+  FD_API_END
+}
+
+int fd_mlp_predict_host(fd_engine* eng, const float* X, int64_t n, int32_t ld, double* prob) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(e.mlp.loaded, FD_ERR_NOT_LOADED, "Model graph_neural (MLP) not loaded");
+  FD_REQUIRE(n >= 0 && n < (1ll << 31), FD_ERR_INVALID_ARG, "batch size out of range");
+  FD_REQUIRE(ld >= e.mlp.dims[0], FD_ERR_INVALID_ARG,
+             "row stride " + std::to_string(ld) + " is below the MLP's in_dim " + std::to_string(e.mlp.dims[0]));
+  if (n == 0) return FD_OK;
+  FD_REQUIRE(X && prob, FD_ERR_INVALID_ARG, "null vectors / output");
+  const size_t xb = (size_t)n * ld * sizeof(float);
+  e.stage_in.ensure(xb);
+  e.stage_out0.ensure((size_t)n * sizeof(double));
+  FD_HIP(hipMemcpyAsync(e.stage_in.ptr, X, xb, hipMemcpyHostToDevice, e.stream));
+  fd::launch_mlp(e, e.stream, e.stage_in.as<float>(), n, ld, e.stage_out0.as<double>());
+  FD_HIP(hipMemcpyAsync(prob, e.stage_out0.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+  FD_HIP(hipStreamSynchronize(e.stream));
+  FD_API_END
+}
+
 int fd_features_seq_device(fd_engine* eng, const fd_txn_batch* txns, int64_t n, float* d_vectors, double* d_raw,
                            float* d_seq) {
   FD_API_BEGIN
@@ -1915,7 +2006,7 @@ int fd_score_records_device(fd_engine* eng, const fd_blend_params* params, const
   FD_REQUIRE(params && slots && n >= 0, FD_ERR_INVALID_ARG, "bad arguments");
   for (int m = 0; m < params->n_models && m < FD_MAX_MODELS; ++m)
     FD_REQUIRE(slots[m] >= 0 || (present && !present[m]), FD_ERR_INVALID_ARG,
-               "routed scoring needs every present model in a forest slot or FD_SLOT_LSTM");
+               "routed scoring needs every present model in a forest slot, FD_SLOT_LSTM or FD_SLOT_MLP");
   if (n == 0) return FD_OK;
   e.feat_vec.ensure((size_t)n * FD_VECTOR_WIDTH * 4);
   e.route_out.ensure((size_t)n * (2 * sizeof(double) + 2));

@@ -267,6 +267,17 @@ struct LstmModel {
   bool hh_finite = false;  // every W_hh weight finite: W_hh h_{-1} = W_hh 0 adds only zeros (lstm_kernel4 skips it)
 };
 
+// MLP head (mlp.hip): the packed model (header, per layer the A operands in the chained k order, padded biases)
+struct MlpModel {
+  bool loaded = false;
+  bool hot = false;  // the reference shape's kernel form: 3 layers, every padded width 64
+  int n_layers = 0;
+  int dims[9] = {};
+  int words = 0;     // 4-B words of the blob (= the kernel's LDS image)
+  int cus = 0, occ_ref = 1, occ_lds = 1;  // CUs; workgroups of each kernel form that fit a CU beside each other
+  DeviceBuffer blob;
+};
+
 // One card's keyed state header (features.hip): 128 B = one L2 line, so a transaction's state read touches one
 // line. Bytes 0-63 hold everything a transaction rewrites (last time, ring cursor, window counts / sums / oldest
 // times, the redis_compat session, the LSTM history cursor in flags), bytes 64-127 what only an insert or a profile
@@ -541,6 +552,8 @@ struct Engine {
   PackedForest forests[kMaxSlots];
   CardStore state;
   LstmModel lstm;
+  MlpModel mlp;
+  unsigned long long mlp_total = 0;  // counter "mlp_launches"
   WindowState windows;
   IngestTables ingest;
   SinkState sink;
@@ -629,6 +642,8 @@ struct Engine {
   int forest_variant = 0;  // "forest_kernel" option
   bool ens_owner_fixed = true;  // "ensemble_owner" option (A/B of the fused kernel's chunk-owner schedule)
   int ens_chunks = 0;           // "ensemble_chunks": 0 auto, 1 wide, 2 compact chunk layout (ensemble.hip)
+  int mlp_form = 0;        // "mlp_form" option: 0 auto, 1 the LDS form (mlp_lds_kernel) for the reference shape too
+  int mlp_wgs_per_cu = 0;  // "mlp_wgs_per_cu" option: the MLP's persistent grid, workgroups per CU (0 auto: 2 where they fit)
   int lstm_rows = 0;  // "lstm_rows" option: transactions per LSTM workgroup tile (0 auto, 4 or 16)
   bool ensemble_on = true;  // "ensemble" option: the fused XGBoost + IsolationForest + blend kernel (auto)
   bool timing = false;
@@ -802,6 +817,10 @@ void load_lstm(Engine& e, const fd_lstm_params& p);
 // (features.hip seq_step); null: every row of d_seq
 void launch_lstm(Engine& e, hipStream_t stream, const float* d_seq, int64_t n, int T, double* d_prob,
                  const unsigned long long* d_desc = nullptr);
+// mlp.hip
+std::vector<uint32_t> pack_mlp_host(const fd_mlp_params& p);  // validates (no device), include/fdengine.h
+void load_mlp(Engine& e, const fd_mlp_params& p);
+void launch_mlp(Engine& e, hipStream_t stream, const float* d_X, int64_t n, int32_t ld, double* d_prob);
 // model_io.hip: the unchanged XGBoost 2.0.3 JSON model file, flattened (fdengine/forest.py semantics)
 struct XgbModel {
   int num_feature = 0;

@@ -142,6 +142,11 @@ class fd_lstm_params(C.Structure):
                 ("b_out", C.c_void_p)]
 
 
+class fd_mlp_params(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("dims", C.c_int32 * 9), ("weight", C.c_void_p * 8),
+                ("bias", C.c_void_p * 8)]
+
+
 class fd_users(C.Structure):
     _fields_ = [("n", C.c_int64), ("key", C.c_void_p), ("avg_amount", C.c_void_p),
                 ("account_age_days", C.c_void_p), ("device_fp", C.c_void_p)]
@@ -163,6 +168,7 @@ FD_TIMING_LSTM = 5
 FD_TIMING_WINDOWS = 6
 FD_TIMING_INGEST = 7
 FD_TIMING_ENSEMBLE = 8
+FD_TIMING_MLP = 9
 
 # JSON ingest codec (fd_ingest_out column order and dtypes)
 INGEST_FIELDS = (("card_key", "<u8"), ("ts_ms", "<i8"), ("amount_cents", "<i8"), ("merchant", "<i4"),
@@ -213,6 +219,7 @@ MERCHANT_WINDOW_DTYPE = [("merchant", "<i4"), ("count", "<i4"), ("window_start",
                          ("pm_mask", "<u8", (4,))]  # the exact moments fd_merchant_windows_merge combines
 FD_MAX_SEQ_LEN = 16
 FD_SLOT_LSTM = 64
+FD_SLOT_MLP = 65
 FD_SEQ_INPUT = 16
 FD_MAX_SHARDS = 64
 FD_ROUTE_RECORD_BYTES = 48
@@ -273,6 +280,12 @@ SIGNATURES = {
     "fd_unload_lstm": (C.c_int, [_vp]),
     "fd_lstm_predict_device": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "fd_lstm_predict_host": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "fd_load_mlp": (C.c_int, [_vp, C.POINTER(fd_mlp_params)]),
+    "fd_unload_mlp": (C.c_int, [_vp]),
+    "fd_mlp_info": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "fd_mlp_predict_device": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "fd_mlp_predict_host": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "fd_pack_mlp_host": (C.c_int, [C.POINTER(fd_mlp_params), _vp, _i64, C.POINTER(_i64)]),
     "fd_features_seq_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _vp, _vp, _vp]),
     "fd_shard_of_host": (C.c_int, [_vp, _i64, _i32, _vp]),
     "fd_route_partition_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _i32, _vp, _vp]),

@@ -431,6 +431,36 @@ class FraudEngine:
     def lstm_predict_device(self, seq_ptr: int, n: int, T: int, prob_ptr: int) -> None:
         N.call("fd_lstm_predict_device", self._h, C.c_void_p(seq_ptr), int(n), int(T), C.c_void_p(prob_ptr))
 
+    # ------------------------------------------------------------------ MLP head (graph_neural, model_type "pytorch")
+    def load_mlp(self, model) -> None:
+        """model: fdengine.mlp.MlpWeights (PyTorch nn.Linear layout, f32)."""
+        p, keep = model.c_struct()
+        N.call("fd_load_mlp", self._h, C.byref(p))
+        del keep
+        self.mlp_info = self.mlp_shape()
+
+    def unload_mlp(self) -> None:
+        N.call("fd_unload_mlp", self._h)
+        self.mlp_info = None
+
+    def mlp_shape(self) -> dict:
+        L, i, h = C.c_int32(), C.c_int32(), C.c_int32()
+        N.call("fd_mlp_info", self._h, C.byref(L), C.byref(i), C.byref(h))
+        return {"n_layers": L.value, "in_dim": i.value, "hidden": h.value}
+
+    def mlp_predict(self, X: np.ndarray) -> np.ndarray:
+        """X: [n, ld] with ld >= in_dim (columns beyond in_dim are not read) -> softmax(model(X))[:, 1] as f64 [n]."""
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2:
+            raise ValueError(f"MLP input must be [n, features], got shape {X.shape}")
+        n, ld = X.shape
+        prob = np.empty(n, np.float64)
+        N.call("fd_mlp_predict_host", self._h, _ptr(X), n, ld, _ptr(prob))
+        return prob
+
+    def mlp_predict_device(self, x_ptr: int, n: int, ld: int, prob_ptr: int) -> None:
+        N.call("fd_mlp_predict_device", self._h, C.c_void_p(x_ptr), int(n), int(ld), C.c_void_p(prob_ptr))
+
     # ------------------------------------------------------------------ card-hash sharding (fdengine/sharding.py)
     def route_partition_device(self, txn_ptrs: dict, n: int, n_shards: int, records_ptr: int, counts_ptr: int) -> None:
         """Group one device-resident micro-batch by owner GPU: n records of FD_ROUTE_RECORD_BYTES at

@@ -248,6 +248,9 @@ class EnsemblePredictor:
                     ok, col = 0, None
             elif slot == N.FD_SLOT_LSTM:
                 ok, slot = 0, -1  # flat vectors carry no sequence: dropped, as the reference's LSTM is
+            elif slot == N.FD_SLOT_MLP:
+                if X.shape[1] != mm.models[name].in_dim:
+                    ok = 0  # torch's matmul raises on another width; the reference drops the model
             elif mm.models[name].kind == "xgboost" and X.shape[1] > mm.models[name].num_feature:
                 ok = 0  # XGBoost rejects wider matrices; the reference drops the model
             elif mm.models[name].kind == "isolation_forest" and X.shape[1] != mm.models[name].num_feature:

@@ -19,11 +19,19 @@ Same public surface — `load_all_models`, `predict(model_name, features) -> np.
                         predict takes [n, T, I] sequences (`_predict_tensorflow` :313-319); a flat
                         scoring vector raises as a Keras LSTM given a 2-D input does
 
+  model_type "pytorch"  graph_neural's state dict (`_load_pytorch_model` :168-179: torch.load + a strict
+                        load_state_dict into the architecture `_create_pytorch_model_architecture` :202-242 builds
+                        from the config's hidden_channels / num_layers) -> the engine's MLP head (fdengine/mlp.py
+                        formats: .pth / .pt state dict, .safetensors, .npz); a file whose shapes differ from the
+                        configured architecture is refused at load (logged, model not loaded), as the reference's
+                        RuntimeError does; predict returns softmax(model(X))[:, 1] as float32
+                        (`_predict_pytorch` :321-330); a width other than the model's raises as torch's matmul does
+
 Everything else keeps the reference's observable behaviour, so the ensemble above sees the same
 model set: a missing model file yields the reference's random DummyModel (:115-118, 244-277);
 its tensorflow / pytorch predict branches fail for a DummyModel exactly as the reference's do
 (:313-331: `predict(..., verbose=0)` / `model(tensor)` raise TypeError) and the ensemble drops
-them; "transformers" returns np.random (:332-336). Real tensorflow / pytorch / transformers model
+them; "transformers" returns np.random (:332-336: nothing to port). Real transformers model
 files are outside this path and are rejected at load (logged, model not loaded).
 """
 from __future__ import annotations
@@ -71,6 +79,24 @@ class EngineLstm:
 
     def __init__(self, input_size: int, hidden: int, n_out: int, path: str):
         self.kind, self.input_size, self.hidden, self.n_out, self.path = "lstm", input_size, hidden, n_out, path
+
+
+class EngineMlp:
+    """The MLP head resident in the engine (one per engine)."""
+
+    def __init__(self, in_dim: int, hidden: int, n_layers: int, path: str):
+        self.kind, self.in_dim, self.hidden, self.n_layers, self.path = "mlp", in_dim, hidden, n_layers, path
+
+
+def load_mlp_checked(path: str, hyperparameters: Optional[dict]):
+    """The graph_neural file's weights, checked against the architecture the reference would build from the
+    config's hyperparameters (hidden_channels, num_layers; defaults 64, 3) before its strict load_state_dict.
+    Pure host logic (no engine)."""
+    from .mlp import HIDDEN, N_LAYERS, check_architecture, load_mlp_file
+    hp = hyperparameters or {}
+    w = load_mlp_file(path)
+    check_architecture(w, hp.get("hidden_channels", HIDDEN), hp.get("num_layers", N_LAYERS))
+    return w
 
 
 def _lstm_weight_file(path: str) -> Optional[str]:
@@ -145,7 +171,7 @@ class ModelManager:
             "loaded_at": self.model_load_times[name].isoformat(),
             "hyperparameters": getattr(cfg, "hyperparameters", {}),
             "preprocessing_steps": getattr(cfg, "preprocessing_steps", []),
-            "engine": (vars(model) if isinstance(model, (EngineForest, EngineLstm)) else None),
+            "engine": (vars(model) if isinstance(model, (EngineForest, EngineLstm, EngineMlp)) else None),
         }
 
     def _load_by_type(self, name: str, cfg):
@@ -162,6 +188,10 @@ class ModelManager:
                 return self._upload(slot, iforest_from_sklearn(model), "isolation_forest", cls)
             # the predict_proba branch: the forest classifiers (anything else raises UnsupportedModel, by class name)
             return self._upload(slot, forest_from_sklearn_classifier(model), "sklearn_classifier", cls)
+        if cfg.model_type == "pytorch":
+            w = load_mlp_checked(cfg.model_path, getattr(cfg, "hyperparameters", None))
+            self.engine.load_mlp(w)
+            return EngineMlp(w.in_dim, w.hidden, w.n_layers, cfg.model_path)
         raise UnsupportedModel(f"model_type {cfg.model_type!r} files are not served by the engine")
 
     def _load_lstm(self, path: str) -> EngineLstm:
@@ -196,6 +226,14 @@ class ModelManager:
             if X.ndim != 3:  # Keras: an LSTM layer needs [batch, timesteps, features]
                 raise ValueError(f"Input 0 of layer lstm is incompatible: expected ndim=3, found ndim={X.ndim}")
             return self.engine.lstm_predict(X).astype(np.float32)
+        if isinstance(model, EngineMlp):
+            X = np.asarray(features)
+            if X.ndim == 1:
+                X = X.reshape(1, -1)
+            if X.ndim != 2 or X.shape[1] != model.in_dim:  # torch's F.linear
+                raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({X.shape[0]}x{X.shape[-1]} and "
+                                   f"{model.in_dim}x{model.hidden})")
+            return self.engine.mlp_predict(X).astype(np.float32)
         if isinstance(model, EngineForest):
             X = np.asarray(features)
             if X.ndim == 1:
@@ -261,10 +299,16 @@ class ModelManager:
             self.engine.unload_forest(m.slot)
         elif isinstance(m, EngineLstm):
             self.engine.unload_lstm()
+        elif isinstance(m, EngineMlp):
+            self.engine.unload_mlp()
 
     def engine_slot(self, model_name: str) -> int:
-        """Engine slot of a device-resident model (FD_SLOT_LSTM for the LSTM head), -1 otherwise."""
+        """Engine slot of a device-resident model (FD_SLOT_LSTM for the LSTM head, FD_SLOT_MLP for the MLP head),
+        -1 otherwise."""
         m = self.models.get(model_name)
+        if isinstance(m, EngineMlp):
+            from ._native import FD_SLOT_MLP
+            return FD_SLOT_MLP
         if isinstance(m, EngineLstm):
             from ._native import FD_SLOT_LSTM
             return FD_SLOT_LSTM
