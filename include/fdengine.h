@@ -413,6 +413,40 @@ int fd_pack_mlp_host(const fd_mlp_params* params, void* blob, int64_t cap, int64
    ml/models/ensemble_predictor.py's per-model predict over the same features). */
 #define FD_SLOT_MLP 65
 
+/* ---------------------------------------------------------------- transaction-network features (graph detector) */
+/* Replaces GraphFraudDetector._add_transaction_to_history + _calculate_network_features
+   (ml/models/graph_neural_network.py:228-242, 338-392): a rolling log of recent transactions, one global arrival
+   sequence per engine, and five features per transaction derived from it. Inputs are fd_txn_batch's card_key
+   (0 = null user_id), merchant (-1 = null merchant_id) and amount_cents, rows in arrival order. Transaction g
+   (0-based since fd_graph_init / fd_graph_clear) sees the entries [s(g), g], itself included, where with
+   H = max_history, keep = ceil(H/2), P = H - keep: s(g) = 0 for g < H, else H + floor((g-H)/P)*P - keep (the
+   reference cuts a full history to its newer half before appending). Later rows of a call see earlier ones; the
+   results do not depend on how the stream is cut into calls. Output row: FD_GRAPH_FEATURES f64 in the order
+   user_centrality, merchant_centrality, clustering_coefficient, path_length_anomaly, community_anomaly; all 0.0 for
+   a row with a null user or merchant (the row still enters the log). Four columns are the reference's values;
+   path_length_anomaly sums the window's amounts exactly in cents where the reference sums floats (differs by less
+   than 1e-11 for positive amounts). network_risk_score (the reference runs its model over torch.randn node
+   features) is not computed. The log is not part of fd_state_snapshot, and is per engine: a sharded deployment
+   keeps one log per rank. */
+#define FD_GRAPH_FEATURES 5
+typedef struct {
+  int32_t max_history; /* the reference's max_history_size (default 10000); 2..65536 */
+} fd_graph_params;
+/* (re)initialises an empty log; FD_ERR_INVALID_ARG for a max_history outside 2..65536 */
+int fd_graph_init(fd_engine* eng, const fd_graph_params* params);
+/* empties the log: the next transaction is g = 0 again. FD_ERR_NOT_LOADED before fd_graph_init (as the calls below) */
+int fd_graph_clear(fd_engine* eng);
+/* total: transactions since init / clear; held: the reference's transaction_history_size, g_last - s(g_last) + 1 */
+int fd_graph_info(fd_engine* eng, int64_t* total, int64_t* held);
+/* Appends n transactions and writes their n x FD_GRAPH_FEATURES rows. _device: device pointers, enqueued on the
+   engine stream, nothing read back. n == 0 does nothing. */
+int fd_graph_step_device(fd_engine* eng, const fd_txn_batch* txns, int64_t n, double* d_out);
+int fd_graph_step_host(fd_engine* eng, const fd_txn_batch* txns, int64_t n, double* out);
+/* The same features for a whole stream from g = 0, on the host alone (no device, no engine): the declared rule by
+   direct scans of each window, with the kernels' epilogue. */
+int fd_graph_features_host(const uint64_t* card_key, const int32_t* merchant, const int64_t* amount_cents, int64_t n,
+                           int32_t max_history, double* out);
+
 /* ---------------------------------------------------------------- batched scoring */
 /* Replaces the per-transaction loop of /batch-predict (ml/main.py:235-249) for prepared scoring
    vectors: every forest model scores the same X, then the blend runs, all on the device.
@@ -734,7 +768,8 @@ enum fd_timing_kind { FD_TIMING_ALL = -1, FD_TIMING_XGB = 0, FD_TIMING_IFOREST =
                       FD_TIMING_BLEND = 3, FD_TIMING_ROUTE = 4, FD_TIMING_LSTM = 5,
                       FD_TIMING_WINDOWS = 6, FD_TIMING_INGEST = 7,
                       FD_TIMING_ENSEMBLE = 8 /* fused XGBoost + IsolationForest + blend kernel */,
-                      FD_TIMING_MLP = 9 /* the MLP head's kernel (fd_mlp_predict_*, FD_SLOT_MLP) */ };
+                      FD_TIMING_MLP = 9 /* the MLP head's kernel (fd_mlp_predict_*, FD_SLOT_MLP) */,
+                      FD_TIMING_GRAPH = 10 /* one fd_graph_step_*: every kernel of its chunks */ };
 int fd_engine_set_timing(fd_engine* eng, int enable);
 /* Engine tuning knobs (for A/B measurement; defaults are the tuned choices):
      "forest_kernel": 0 auto, 1 force the 256-thread kernel, 2 force the 1024-thread tree-split kernel
@@ -796,7 +831,7 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    fd_score_records_pipelined so far), "pipelined_compact_batches" (of those, scored by the fused ensemble kernel from
    the compact 64-B rows: no vectors requested), "ensemble_single_launches" (fd_forest_predict batches scored by the
    fused kernel over one forest), "forest_sparse_launches" (launches of the sparse-layout forest kernel),
-   "mlp_launches" (launches of the MLP head's kernel),
+   "mlp_launches" (launches of the MLP head's kernel), "graph_steps" (fd_graph_step_* calls with n > 0),
    "pipelined_slot_stream_batches" (of those, with the slot pass on
    its own stream), "pipelined_host_ns" (host nanoseconds inside fd_score_batch_pipelined), "sharded_steps" (fd_sharded_step calls), "rccl_ops" (RCCL operations the exchanges issued: sends, receives,
    all-gathers) and "sharded_host_ns_<phase>" (host

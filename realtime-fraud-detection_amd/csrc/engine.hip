@@ -9,6 +9,7 @@
 
 #include "blend_row.h"
 #include "fd_internal.h"
+#include "graph_row.h"
 #include "ingest_parse.h"
 
 namespace fd {
@@ -349,6 +350,7 @@ int fd_engine_destroy(fd_engine* eng) {
   e.feat_in.release();
   fd::windows_release(e);
   fd::sink_release(e);
+  fd::graph_release(e);
   for (auto* b : {&e.route_blk, &e.route_blk_stream, &e.route_out, &e.route_err, &e.seq_buf, &e.seq_desc, &e.lstm.wpk, &e.lstm.wpk4, &e.lstm.bias,
                   &e.lstm.wout, &e.lstm.bout, &e.state.seq, &e.mlp.blob})
     b->release();
@@ -490,6 +492,8 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
     *value = (int64_t)e.sparse_total;
   } else if (k == "mlp_launches") {  // launches of the MLP head's kernel (fd_mlp_predict_*, FD_SLOT_MLP models)
     *value = (int64_t)e.mlp_total;
+  } else if (k == "graph_steps") {  // fd_graph_step_* calls that appended transactions
+    *value = (int64_t)e.graph.steps;
   } else if (k == "latency_prebinned_batches") {  // latency pair launches that used the feature kernel's bins
     *value = (int64_t)e.prebin_total;
   } else if (k == "pipelined_split_batches") {  // of the compact ones: split rows (compact_vectors 2)
@@ -1935,6 +1939,82 @@ int fd_mlp_predict_host(fd_engine* eng, const float* X, int64_t n, int32_t ld, d
   fd::launch_mlp(e, e.stream, e.stage_in.as<float>(), n, ld, e.stage_out0.as<double>());
   FD_HIP(hipMemcpyAsync(prob, e.stage_out0.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e.stream));
   FD_HIP(hipStreamSynchronize(e.stream));
+  FD_API_END
+}
+
+int fd_graph_init(fd_engine* eng, const fd_graph_params* params) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "null params");
+  FD_HIP(hipStreamSynchronize(e.stream));  // a step in flight may still read the log this replaces
+  fd::graph_init(e, *params);
+  FD_API_END
+}
+
+int fd_graph_clear(fd_engine* eng) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  fd::graph_clear(e);
+  FD_API_END
+}
+
+int fd_graph_info(fd_engine* eng, int64_t* total, int64_t* held) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E_quiet(eng);
+  fd::graph_info(e, total, held);
+  FD_API_END
+}
+
+int fd_graph_step_device(fd_engine* eng, const fd_txn_batch* txns, int64_t n, double* d_out) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(txns, FD_ERR_INVALID_ARG, "null txns");
+  fd::graph_step(e, *txns, n, d_out);
+  FD_API_END
+}
+
+int fd_graph_step_host(fd_engine* eng, const fd_txn_batch* txns, int64_t n, double* out) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(txns, FD_ERR_INVALID_ARG, "null txns");
+  FD_REQUIRE(e.graph.ready, FD_ERR_NOT_LOADED, "graph log not initialised (fd_graph_init)");
+  FD_REQUIRE(n >= 0 && n < (1ll << 31), FD_ERR_INVALID_ARG, "batch size out of range");
+  if (n == 0) return FD_OK;
+  FD_REQUIRE(txns->card_key && txns->merchant && txns->amount_cents && out, FD_ERR_INVALID_ARG,
+             "null card_key / merchant / amount_cents / output");
+  const size_t seg8 = (size_t)n * 8;
+  e.stage_in.ensure(2 * seg8 + (size_t)n * 4);
+  e.stage_out0.ensure((size_t)n * FD_GRAPH_FEATURES * sizeof(double));
+  char* b = e.stage_in.as<char>();
+  fd_txn_batch d{};
+  FD_HIP(hipMemcpyAsync(b, txns->card_key, seg8, hipMemcpyHostToDevice, e.stream));
+  FD_HIP(hipMemcpyAsync(b + seg8, txns->amount_cents, seg8, hipMemcpyHostToDevice, e.stream));
+  FD_HIP(hipMemcpyAsync(b + 2 * seg8, txns->merchant, (size_t)n * 4, hipMemcpyHostToDevice, e.stream));
+  d.card_key = reinterpret_cast<const uint64_t*>(b);
+  d.amount_cents = reinterpret_cast<const int64_t*>(b + seg8);
+  d.merchant = reinterpret_cast<const int32_t*>(b + 2 * seg8);
+  fd::graph_step(e, d, n, e.stage_out0.as<double>());
+  FD_HIP(hipMemcpyAsync(out, e.stage_out0.ptr, (size_t)n * FD_GRAPH_FEATURES * sizeof(double), hipMemcpyDeviceToHost,
+                        e.stream));
+  FD_HIP(hipStreamSynchronize(e.stream));
+  FD_API_END
+}
+
+int fd_graph_features_host(const uint64_t* card_key, const int32_t* merchant, const int64_t* amount_cents, int64_t n,
+                           int32_t max_history, double* out) {
+  FD_API_BEGIN
+  FD_REQUIRE(max_history >= fd::kGraphMinHistory && max_history <= fd::kGraphMaxHistory, FD_ERR_INVALID_ARG,
+             "graph max_history must be in [2, 65536], got " + std::to_string(max_history));
+  FD_REQUIRE(n >= 0, FD_ERR_INVALID_ARG, "negative n");
+  if (n == 0) return FD_OK;
+  FD_REQUIRE(card_key && merchant && amount_cents && out, FD_ERR_INVALID_ARG,
+             "null card_key / merchant / amount_cents / output");
+  fd::graph_features_stream_host(card_key, merchant, amount_cents, n, max_history, out);
   FD_API_END
 }
 

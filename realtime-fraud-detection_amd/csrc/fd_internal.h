@@ -267,6 +267,22 @@ struct LstmModel {
   bool hh_finite = false;  // every W_hh weight finite: W_hh h_{-1} = W_hh 0 adds only zeros (lstm_kernel4 skips it)
 };
 
+// Transaction-network features (graph.hip): the device log of recent transactions. Each of the two buffers holds the
+// four columns (card_key u64, cents i64, merchant i32, dist i32) at `cap` entries; the live one holds the global
+// indices [base, total). The tail is carried to the other buffer when the window start steps.
+constexpr int kGraphChunk = 16384;  // transactions per pass of the graph kernels (temporaries stay at chunk + H)
+struct GraphState {
+  bool ready = false;
+  int H = 0;    // max_history
+  int cap = 0;  // entries per column: H + kGraphChunk
+  int cur = 0;  // the live buffer
+  int64_t total = 0;  // transactions since init / clear: the next global index
+  int64_t base = 0;   // global index of the live buffer's position 0
+  DeviceBuffer log[2];
+  DeviceBuffer dm;  // per transaction of a chunk: dM, the scan kernel's count for the cluster kernel
+  unsigned long long steps = 0;  // counter "graph_steps"
+};
+
 // MLP head (mlp.hip): the packed model (header, per layer the A operands in the chained k order, padded biases)
 struct MlpModel {
   bool loaded = false;
@@ -554,6 +570,7 @@ struct Engine {
   LstmModel lstm;
   MlpModel mlp;
   unsigned long long mlp_total = 0;  // counter "mlp_launches"
+  GraphState graph;
   WindowState windows;
   IngestTables ingest;
   SinkState sink;
@@ -821,6 +838,12 @@ void launch_lstm(Engine& e, hipStream_t stream, const float* d_seq, int64_t n, i
 std::vector<uint32_t> pack_mlp_host(const fd_mlp_params& p);  // validates (no device), include/fdengine.h
 void load_mlp(Engine& e, const fd_mlp_params& p);
 void launch_mlp(Engine& e, hipStream_t stream, const float* d_X, int64_t n, int32_t ld, double* d_prob);
+// graph.hip
+void graph_init(Engine& e, const fd_graph_params& p);
+void graph_clear(Engine& e);
+void graph_release(Engine& e);
+void graph_info(Engine& e, int64_t* total, int64_t* held);
+void graph_step(Engine& e, const fd_txn_batch& t, int64_t n, double* d_out);  // device pointers, on e.stream
 // model_io.hip: the unchanged XGBoost 2.0.3 JSON model file, flattened (fdengine/forest.py semantics)
 struct XgbModel {
   int num_feature = 0;

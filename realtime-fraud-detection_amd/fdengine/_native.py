@@ -147,6 +147,10 @@ class fd_mlp_params(C.Structure):
                 ("bias", C.c_void_p * 8)]
 
 
+class fd_graph_params(C.Structure):
+    _fields_ = [("max_history", C.c_int32)]
+
+
 class fd_users(C.Structure):
     _fields_ = [("n", C.c_int64), ("key", C.c_void_p), ("avg_amount", C.c_void_p),
                 ("account_age_days", C.c_void_p), ("device_fp", C.c_void_p)]
@@ -169,6 +173,7 @@ FD_TIMING_WINDOWS = 6
 FD_TIMING_INGEST = 7
 FD_TIMING_ENSEMBLE = 8
 FD_TIMING_MLP = 9
+FD_TIMING_GRAPH = 10
 
 # JSON ingest codec (fd_ingest_out column order and dtypes)
 INGEST_FIELDS = (("card_key", "<u8"), ("ts_ms", "<i8"), ("amount_cents", "<i8"), ("merchant", "<i4"),
@@ -220,6 +225,9 @@ MERCHANT_WINDOW_DTYPE = [("merchant", "<i4"), ("count", "<i4"), ("window_start",
 FD_MAX_SEQ_LEN = 16
 FD_SLOT_LSTM = 64
 FD_SLOT_MLP = 65
+FD_GRAPH_FEATURES = 5
+GRAPH_COLUMNS = ("user_centrality", "merchant_centrality", "clustering_coefficient", "path_length_anomaly",
+                 "community_anomaly")
 FD_SEQ_INPUT = 16
 FD_MAX_SHARDS = 64
 FD_ROUTE_RECORD_BYTES = 48
@@ -286,6 +294,12 @@ SIGNATURES = {
     "fd_mlp_predict_device": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "fd_mlp_predict_host": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "fd_pack_mlp_host": (C.c_int, [C.POINTER(fd_mlp_params), _vp, _i64, C.POINTER(_i64)]),
+    "fd_graph_init": (C.c_int, [_vp, C.POINTER(fd_graph_params)]),
+    "fd_graph_clear": (C.c_int, [_vp]),
+    "fd_graph_info": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "fd_graph_step_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _vp]),
+    "fd_graph_step_host": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _vp]),
+    "fd_graph_features_host": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
     "fd_features_seq_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _vp, _vp, _vp]),
     "fd_shard_of_host": (C.c_int, [_vp, _i64, _i32, _vp]),
     "fd_route_partition_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _i32, _vp, _vp]),

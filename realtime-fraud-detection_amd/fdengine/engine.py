@@ -461,6 +461,39 @@ class FraudEngine:
     def mlp_predict_device(self, x_ptr: int, n: int, ld: int, prob_ptr: int) -> None:
         N.call("fd_mlp_predict_device", self._h, C.c_void_p(x_ptr), int(n), int(ld), C.c_void_p(prob_ptr))
 
+    # ------------------------------------------------------------------ transaction-network features (graph detector)
+    def graph_init(self, max_history: int = 10000) -> None:
+        """An empty transaction log of the reference's max_history_size (GraphFraudDetector, 2..65536)."""
+        p = N.fd_graph_params(int(max_history))
+        N.call("fd_graph_init", self._h, C.byref(p))
+
+    def graph_clear(self) -> None:
+        N.call("fd_graph_clear", self._h)
+
+    def graph_info(self) -> dict:
+        total, held = C.c_int64(), C.c_int64()
+        N.call("fd_graph_info", self._h, C.byref(total), C.byref(held))
+        return {"total": total.value, "held": held.value}
+
+    def graph_step(self, card_key, merchant, amount_cents) -> np.ndarray:
+        """Host columns in arrival order (card_key 0 = null user, merchant -1 = null merchant) -> f64 [n, 5] in
+        fdengine._native.GRAPH_COLUMNS order; the rows enter the log."""
+        cols = {"card_key": np.ascontiguousarray(card_key, np.uint64),
+                "merchant": np.ascontiguousarray(merchant, np.int32),
+                "amount_cents": np.ascontiguousarray(amount_cents, np.int64)}
+        n = len(cols["card_key"])
+        if len(cols["merchant"]) != n or len(cols["amount_cents"]) != n:
+            raise ValueError("graph_step columns differ in length")
+        out = np.empty((n, N.FD_GRAPH_FEATURES), np.float64)
+        b = N.fd_txn_batch(**{f: c.ctypes.data for f, c in cols.items()})
+        N.call("fd_graph_step_host", self._h, C.byref(b), n, _ptr(out))
+        return out
+
+    def graph_step_device(self, ptrs: dict, n: int, out_ptr: int) -> None:
+        """ptrs: device pointers of card_key, merchant and amount_cents; out_ptr: f64 [n, 5]; on the engine stream."""
+        b = N.fd_txn_batch(**{f: int(ptrs[f]) for f in ("card_key", "merchant", "amount_cents")})
+        N.call("fd_graph_step_device", self._h, C.byref(b), int(n), C.c_void_p(out_ptr) if out_ptr else None)
+
     # ------------------------------------------------------------------ card-hash sharding (fdengine/sharding.py)
     def route_partition_device(self, txn_ptrs: dict, n: int, n_shards: int, records_ptr: int, counts_ptr: int) -> None:
         """Group one device-resident micro-batch by owner GPU: n records of FD_ROUTE_RECORD_BYTES at
