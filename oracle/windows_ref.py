@@ -21,6 +21,10 @@ Declared deviations from the Java arithmetic: amounts are exact integer cents (t
 the merchant std-dev is the exact-moment formula sqrt((n S2 - S1^2) / n^2) / 100 (Java: two-pass f64
 mean / average of squared deviations; agrees to ~1e-15 relative, see java_stddev below). Transactions
 with an unknown merchant (-1) are not aggregated by merchant.
+first_ts (the accumulator's windowStart, 0 = unset): Java's `windowStart == 0 || ts < windowStart` makes an event
+at exactly 0 ms unset it again, so the result depends on when that event arrives; the engine folds in key order,
+not arrival order. Declared: the smallest non-zero event time, 0 if there is none. This is the Java result whenever
+the event at 0 arrives before the window's later ones, and whenever the window also holds a negative time.
 PARITY UNPINNED: no JDK / Flink here and the reference has no tests or fixtures for these functions.
 """
 from __future__ import annotations
@@ -149,7 +153,7 @@ class WindowOracle:
         pms = {e["pm"] for e in evs if e["pm"] != 255}
         first = last = 0
         for e in evs:                                # accumulator windowStart / windowEnd rule
-            if first == 0 or e["ts"] < first:
+            if e["ts"] != 0 and (first == 0 or e["ts"] < first):   # declared: see the header
                 first = e["ts"]
             if e["ts"] > last:
                 last = e["ts"]

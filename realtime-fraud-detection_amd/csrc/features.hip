@@ -621,6 +621,10 @@ __device__ __forceinline__ void store_card(CardHeader* h, const CardRegs& c) {
 }
 
 // windows as of time t from the (time-sorted) ring: the newest events with ts > t - W
+// The `>` below, and the same test in process_long's final header rebuild, cannot be told from `>=` by any output:
+// the one extra event would sit at exactly t - W, nothing reads the rebuilt windows before the card's next
+// incremental step, and that step evicts it first (wo <= ts - W with ts >= t). No test can pin these two; the edges
+// that outputs do depend on are pinned by tests/test_gpu_velocity_edges.py.
 __device__ void rebuild_windows(CardRegs& c, const RingEvent* __restrict__ rg, int K, long long t) {
 #pragma unroll
   for (int w = 0; w < 3; ++w) {

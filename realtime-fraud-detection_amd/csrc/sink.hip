@@ -121,7 +121,10 @@ __global__ void __launch_bounds__(256) sink_update_kernel(AggEntry* T, unsigned 
     if (kind == 3) {
       unsigned long long kk = key[i];
       if (kk == 0ull) kk = 1ull;  // the card table's key normalisation
-      const unsigned long long tag = smix(smix(kk) ^ ((unsigned long long)(m + 1) << 32 | (unsigned long long)hour)) | 1ull;
+      // the hour's low 32 bits, as in agg_key: a negative hour (an event before 1970) sign-extended over the
+      // merchant's bits would give one member to every merchant of that hour
+      const unsigned long long tag =
+          smix(smix(kk) ^ ((unsigned long long)(m + 1) << 32 | ((unsigned long long)hour & 0xFFFFFFFFull))) | 1ull;
       const int r = user_insert(U, umask, tag, hour);
       if (r < 0) {
         atomicOr(err, 2u);

@@ -179,7 +179,9 @@ __global__ void __launch_bounds__(256) win_reduce_user_kernel(const WinEvent* __
       prev_m = mk;
     }
     if (e.pm != 255) pm[e.pm >> 6] |= 1ull << (e.pm & 63);
-    if (first == 0 || e.ts < first) first = e.ts;  // accumulator.windowStart (0 = unset)
+    // accumulator.windowStart (0 = unset). This fold runs in key order, not arrival order, so an event at exactly
+    // 0 ms never sets it (the Java rule would depend on when it arrives): the smallest non-zero time, 0 if none
+    if (e.ts != 0 && (first == 0 || e.ts < first)) first = e.ts;
     if (e.ts > last) last = e.ts;                  // accumulator.windowEnd
   }
   const long long m = (long long)((seg) & 0xFFFFull) + base_min;
@@ -280,7 +282,7 @@ __global__ void __launch_bounds__(256) win_reduce_merchant_kernel(const WinEvent
       prev_u = uk;
     }
     if (e.pm != 255) pm[e.pm >> 6] |= 1ull << (e.pm & 63);
-    if (first == 0 || e.ts < first) first = e.ts;
+    if (e.ts != 0 && (first == 0 || e.ts < first)) first = e.ts;  // as win_reduce_user_kernel
     if (e.ts > last) last = e.ts;
   }
   const long long hr = (long long)(seg & 0xFFFFull) + base_hour;

@@ -110,3 +110,44 @@ def test_sink_capacity_error(engine):
     engine.sink_init(16, 1 << 12)
     with pytest.raises(NativeError, match="aggregate table full"):
         engine.sink_update_host(b["key"], b["ts_ms"], b["amount_cents"], b["merchant"])
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_sink_time_and_score_edges(engine, device):
+    """tests/window_edge_cases.py: event times around 0, +-1 h and +-1 day (hour key 0 takes (-1 h, 1 h): Java
+    division truncates), on the window streams' minute and hour edges, fraud scores of 0.7, the next float up
+    and NaN, the threshold batch's hot merchants"""
+    import torch
+
+    import window_edge_cases as WE
+    engine.sink_init(1 << 12, 1 << 14)
+    o = SinkOracle()
+    for b in WE.sink_batches() + WE.watermark_batches(0) + WE.threshold_batches(WE.T0):
+        if device:
+            t = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in b.items()}
+            engine.sink_update_device({"card_key": t["key"].data_ptr(), "ts_ms": t["ts_ms"].data_ptr(),
+                                       "amount_cents": t["amount_cents"].data_ptr(),
+                                       "merchant": t["merchant"].data_ptr()}, len(b["key"]),
+                                      {"is_fraud": t["is_fraud"].data_ptr(), "fraud_score": t["fraud_score"].data_ptr()})
+        else:
+            engine.sink_update_host(b["key"], b["ts_ms"], b["amount_cents"], b["merchant"], b["is_fraud"],
+                                    b["fraud_score"])
+        o.run_batch(b)
+    nh, nd, nm = _check(engine, o)
+    assert {"hourly:0", "hourly:-1", "hourly:1", "hourly:-24", "hourly:24", "daily:0", "daily:-1", "daily:1"} <= set(o.redis)
+    assert o.redis["hourly:0"]["high_risk_count"] > 0 and nm > 10
+
+
+def test_sink_negative_hour_users_per_merchant(engine):
+    """The minimal case behind a mismatch the edge batches found: two merchants, the same two cards, one hour
+    before 1970. The distinct-user set's tag mixed the sign-extended hour over the merchant's bits, so the second
+    merchant of a negative hour found its cards already present (unique_user_count 0 against 2)."""
+    import window_edge_cases as WE
+    engine.sink_init(1 << 10, 1 << 10)
+    o = SinkOracle()
+    b = WE._batch([(key, -3_600_000 - 5 * q, 100, m, 0, 0, 0.5) for q, (key, m) in
+                   enumerate(((11, 1), (12, 1), (11, 2), (12, 2)))])
+    engine.sink_update_host(b["key"], b["ts_ms"], b["amount_cents"], b["merchant"], b["is_fraud"], b["fraud_score"])
+    o.run_batch(b)
+    assert o.redis["merchant:1:-1"]["unique_user_count"] == 2 and o.redis["merchant:2:-1"]["unique_user_count"] == 2
+    _check(engine, o)

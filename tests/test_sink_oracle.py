@@ -28,3 +28,36 @@ def test_hourly_daily_merchant_known_answers():
     assert m["unique_user_count"] == 1 and m["total_count"] == 2
     assert f"merchant:None:{h2}" not in o.redis and not any(k.endswith(f":{h2}") and k.startswith("merchant")
                                                              for k in o.redis)
+
+
+def test_negative_times_truncate_toward_zero_and_score_edge():
+    """hour key 0 takes (-3 600 000, 3 600 000) and day key 0 (-86 400 000, 86 400 000): Java long division;
+    fraudScore > 0.7 is strict, a null score counts nothing"""
+    import numpy as np
+    up = float(np.nextafter(0.7, 1.0))
+    o = SinkOracle()
+    o.process(1, 1.0, -(H - 1), 2, False, 0.7)
+    o.process(1, 2.0, H - 1, 2, True, up)
+    o.process(2, 4.0, -H, 2, False, None)
+    o.process(2, 8.0, H, None, False, 0.71)
+    o.process(3, 16.0, -86_400_000, 2, False, None)
+    a = o.redis["hourly:0"]
+    assert (a["total_count"], a["total_amount"], a["fraud_count"], a["high_risk_count"]) == (2, 3.0, 1, 1)
+    assert o.redis["hourly:-1"]["total_count"] == 1 and o.redis["hourly:1"]["high_risk_count"] == 1
+    assert o.redis["hourly:-24"]["total_count"] == 1
+    assert o.redis["daily:0"]["total_count"] == 4 and o.redis["daily:-1"]["total_count"] == 1
+    assert o.redis["merchant:2:0"]["unique_user_count"] == 1 and o.redis["merchant:2:-1"]["total_count"] == 1
+    assert "merchant:None:1" not in o.redis
+
+
+def test_edge_batches_hold_every_edge():
+    import numpy as np
+
+    import window_edge_cases as WE
+    ts = np.concatenate([b["ts_ms"] for b in WE.sink_batches()])
+    for unit in (H, 86_400_000):
+        for s in (-1, 1):
+            assert {s * (unit - 1), s * unit, s * (unit + 1)} <= set(ts.tolist())
+    assert {-1, 0, 1} <= set(ts.tolist())
+    sc = np.concatenate([b["fraud_score"] for b in WE.sink_batches()])
+    assert (sc == 0.7).any() and (sc == WE.SCORE_UP).any() and np.isnan(sc).any()

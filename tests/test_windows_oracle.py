@@ -98,3 +98,100 @@ def test_empty_and_no_advance():
     wm = o.wm
     assert o.step([ev(1, T0 - 50_000, 1)]) == ([], [])   # older batch max: watermark does not regress
     assert o.wm == wm
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the exact time and value edges (tests/window_edge_cases.py feeds the same to the device)
+
+def test_watermark_on_end_minus_two_minus_one_and_end():
+    E = T0 + 60_000
+    o = W.WindowOracle()
+    assert o.step([ev(1, T0 + 1, 100)]) == ([], [])
+    assert o.step([ev(2, E + 9_999, 1)]) == ([], []) and o.wm == E - 2   # end - 1 = E - 1 > watermark: not yet
+    u, m = o.step([ev(2, E + 10_000, 1)])                               # watermark E - 1 = end - 1: fires
+    assert o.wm == E - 1 and m == []
+    assert [(r["user_key"], r["window_start"], r["window_end"], r["count"]) for r in u] == [(1, E - 300_000, E, 1)]
+    assert o.step([ev(2, E + 10_001, 1)]) == ([], []) and o.wm == E     # nothing ends in (E - 1, E]
+
+
+def test_late_event_newest_window_at_the_watermark():
+    E = T0 + 60_000
+    o = W.WindowOracle()
+    o.step([ev(9, E + 9_999, 1)])                                       # watermark E - 2
+    # late by minutes: newest window of E - 300 000 is [E - 300 000, E), end - 1 = watermark + 1: still open;
+    # 1 ms earlier the newest window ended at E - 60 000: dropped
+    assert o.step([ev(1, E - 300_000, 10), ev(2, E - 300_001, 10)]) == ([], [])
+    u, _ = o.step([ev(9, E + 10_000, 1)])                               # watermark E - 1
+    assert [(r["user_key"], r["window_start"], r["count"], r["total_amount"]) for r in u] == [(1, E - 300_000, 1, 0.1)]
+    o.step([ev(3, E - 300_000, 5)])                                     # now end - 1 == watermark: dropped
+    u, _ = o.step([], flush=True)
+    assert {r["user_key"] for r in u} == {9}
+
+
+def test_negative_event_times_floor():
+    o = W.WindowOracle()
+    o.step([ev(1, -1, 100, merchant=4), ev(2, 0, 100, merchant=4)])
+    u, m = o.step([], flush=True)
+    assert sorted(r["window_start"] for r in u if r["user_key"] == 1) == [-300_000, -240_000, -180_000, -120_000, -60_000]
+    assert sorted(r["window_start"] for r in u if r["user_key"] == 2) == [-240_000, -180_000, -120_000, -60_000, 0]
+    assert sorted((r["window_start"], r["window_end"], r["count"]) for r in m) == [(-3_600_000, 0, 1), (0, 3_600_000, 1)]
+    # the accumulator's first_ts rule treats 0 as "unset": restated as written
+    assert [r["first_ts"] for r in m if r["window_start"] == 0] == [0]
+
+
+def test_score_thresholds_are_strict():
+    assert W.velocity_score(5, 100_000, 0, 1) == 0.0                    # 5, 1000.00 and 1 / 5 = 0.2: none crossed
+    assert W.velocity_score(6, 100_001, 0, 1) == 0.1 + 0.1 + 0.0 + 0.2
+    assert W.velocity_score(10, 500_000, 0, 2) == 0.1 + 0.1
+    assert W.velocity_score(11, 500_001, 0, 2) == 0.2 + 0.2 + 0.0 + 0.2
+    assert W.velocity_score(20, 1_000_000, 0, 4) == 0.2 + 0.2
+    assert W.velocity_score(21, 1_000_001, 0, 4) == 0.4 + 0.3 + 0.0 + 0.2
+    assert W.merchant_risk(500, 0.0, 1.0, 0.0, 50) == 0.0               # 500 and 50 / 500 = 0.1: none crossed
+    assert W.merchant_risk(501, 0.0, 1.0, 0.0, 50) == 0.0 + 0.1 + 0.3
+    assert W.merchant_risk(1000, 0.0, 1.0, 0.0, 100) == 0.0 + 0.1
+    assert W.merchant_risk(1001, 0.0, 1.0, 0.0, 100) == 0.0 + 0.2 + 0.3
+    o = W.WindowOracle()
+    up = float(np.nextafter(0.7, 1.0))
+    o.step([ev(1, T0, 1, score=0.7), ev(1, T0 + 1, 1, score=up), ev(1, T0 + 2, 1)])
+    u, m = o.step([], flush=True)
+    assert {r["high_risk_count"] for r in u} == {1} and m[0]["high_risk_count"] == 1
+
+
+def test_edge_streams_hold_every_edge():
+    """the streams the GPU tests replay: each listed edge at least once"""
+    import window_edge_cases as WE
+    for base in (WE.T0, 0):
+        edges = WE.time_edges(WE.watermark_batches(base))
+        print(base, edges)
+        assert all(v >= 1 for k, v in edges.items() if k != "negative_ts"), edges
+        assert (edges["negative_ts"] >= 1) == (base == 0)
+    o = W.WindowOracle()
+    o.step(WE.oracle_batch(WE.threshold_batches(WE.T0)[0]))
+    u, m = o.step([], flush=True)
+    assert {5, 6, 10, 11, 20, 21} <= {r["count"] for r in u}
+    assert {100_000, 100_001, 500_000, 500_001, 1_000_000, 1_000_001} <= {round(r["total_amount"] * 100) for r in u}
+    assert {(5, 1), (10, 2), (20, 4)} <= {(r["count"], r["unique_merchants"]) for r in u}     # exactly 0.2
+    assert {(6, 1), (11, 2), (21, 4)} <= {(r["count"], r["unique_merchants"]) for r in u}     # below it
+    assert {(500, 50), (501, 50), (1000, 100), (1001, 100)} <= {(r["count"], r["unique_users"]) for r in m}
+    # the scores on both sides of every threshold differ by the step
+    by = {(r["count"], r["unique_merchants"]): r["velocity_score"] for r in u if r["user_key"] in range(101, 107)}
+    assert by[6, 1] > by[5, 1] and by[11, 2] > by[10, 2] and by[21, 4] > by[20, 4]
+    risk = {r["count"]: r["risk_score"] for r in m if r["merchant"] in (40, 41, 42, 43)}
+    assert risk[501] - risk[500] > 0.39 and risk[1001] - risk[1000] > 0.39                    # + 0.1 and + 0.3
+    scores = WE.threshold_batches(WE.T0)[0]["fraud_score"]
+    assert (scores == 0.7).any() and (scores == WE.SCORE_UP).any() and np.isnan(scores).any()
+
+
+def test_first_ts_ignores_an_event_at_time_zero():
+    """declared (module header): an event at exactly 0 ms never sets first_ts, in any arrival order"""
+    for order in ((5, 0, 7), (0, 5, 7), (7, 5, 0)):
+        o = W.WindowOracle()
+        o.step([ev(1, t, 1, merchant=2) for t in order])
+        u, m = o.step([], flush=True)
+        assert [r["first_ts"] for r in m] == [5] and [r["last_ts"] for r in m] == [7]
+        assert {r["first_ts"] for r in u if r["window_start"] == 0} == {5}
+    o = W.WindowOracle()
+    o.step([ev(1, 0, 1, merchant=2), ev(1, -3, 1, merchant=2)])
+    u, m = o.step([], flush=True)
+    assert {r["window_start"]: r["first_ts"] for r in m} == {0: 0, -3_600_000: -3}
+    assert {r["first_ts"] for r in u if r["window_start"] == -60_000} == {-3}
