@@ -447,6 +447,48 @@ int fd_graph_step_host(fd_engine* eng, const fd_txn_batch* txns, int64_t n, doub
 int fd_graph_features_host(const uint64_t* card_key, const int32_t* merchant, const int64_t* amount_cents, int64_t n,
                            int32_t max_history, double* out);
 
+/* ---------------------------------------------------------------- text patterns and features (text analyzer) */
+/* Replaces BertTextAnalyzer.detect_fraud_patterns and get_text_features (ml/models/bert_text_analyzer.py:283-399).
+   A row is four UTF-8 fields in the fixed order merchant_name (m), description (d), category (c), location (l); a
+   missing key is the empty field. The rows of a call are one byte blob and 4n + 1 offsets into it.
+   Domain: rows whose four fields are all ASCII (every byte < 0x80). Any other row gets status FD_TEXT_NONASCII and
+   all its outputs are 0 (exactness there needs Unicode tables: str.lower(), \d as category Nd, Unicode whitespace);
+   fdengine.text.BertTextAnalyzer recomputes such rows on the host by the reference's rule.
+   Byte classes (ASCII): space = 0x09-0x0D, 0x1C-0x1F, 0x20 (Python's \s and str.split()); digit = 0-9; alpha = a-z,
+   A-Z; special = everything else, 0x00-0x08, 0x0E-0x1B and 0x7F included (a NUL is an ordinary byte: fields are
+   delimited by offsets).
+   Features, FD_TEXT_FEATURES f64 per row in the reference's dict order: merchant_name_length, description_length,
+   total_text_length, merchant_name_unique_chars (distinct byte values of m after folding A-Z onto a-z),
+   merchant_name_char_diversity (unique / length as one f64 division; both 0 for an empty m), numbers_in_merchant,
+   numbers_in_description, total_numbers, special_chars_merchant, special_chars_description, total_special_chars,
+   merchant_word_count (maximal runs of non-space bytes), description_word_count, total_word_count.
+   Patterns, one byte per row: bit 0 crypto_keywords, 1 gift_card_keywords, 2 urgent_language, 3 suspicious_merchant,
+   4 known_scam_patterns; a bit is set when any keyword of its list (csrc/text_row.h, 45 in all) is a substring of
+   m ' ' d ' ' c ' ' l with A-Z folded onto a-z: all three separators always present, no word boundaries, a keyword
+   may span fields, a space inside a keyword is 0x20 only.
+   A field is shorter than 2^32 bytes. analyze_transaction_text (a model fetched by name, random logits without it)
+   is not computed. */
+#define FD_TEXT_FIELDS 4
+#define FD_TEXT_PATTERNS 5
+#define FD_TEXT_FEATURES 14
+#define FD_TEXT_NONASCII 1
+typedef struct {
+  const uint8_t* bytes;
+  const int64_t* off; /* 4n + 1 entries, off[0] = 0, non-decreasing; row i, field j occupies
+                         [off[4i+j], off[4i+j+1]) of bytes */
+} fd_text_batch;
+/* n x FD_TEXT_FEATURES features, n pattern bytes, n status bytes; any output may be NULL; n == 0 does nothing.
+   _device: device pointers, enqueued on the engine stream, nothing read back (the offsets are not checked).
+   _host: host pointers; FD_ERR_INVALID_ARG for a nonzero off[0] or decreasing offsets. */
+int fd_text_features_device(fd_engine* eng, const fd_text_batch* d, int64_t n, double* d_feat, uint8_t* d_patterns,
+                            uint8_t* d_status);
+int fd_text_features_host(fd_engine* eng, const fd_text_batch* t, int64_t n, double* feat, uint8_t* patterns,
+                          uint8_t* status);
+/* The same on the host alone (no device, no engine): the declared rule by direct scans, each keyword searched for in
+   the joined text. */
+int fd_text_features_ref_host(const uint8_t* bytes, const int64_t* off, int64_t n, double* feat, uint8_t* patterns,
+                              uint8_t* status);
+
 /* ---------------------------------------------------------------- batched scoring */
 /* Replaces the per-transaction loop of /batch-predict (ml/main.py:235-249) for prepared scoring
    vectors: every forest model scores the same X, then the blend runs, all on the device.
@@ -769,7 +811,8 @@ enum fd_timing_kind { FD_TIMING_ALL = -1, FD_TIMING_XGB = 0, FD_TIMING_IFOREST =
                       FD_TIMING_WINDOWS = 6, FD_TIMING_INGEST = 7,
                       FD_TIMING_ENSEMBLE = 8 /* fused XGBoost + IsolationForest + blend kernel */,
                       FD_TIMING_MLP = 9 /* the MLP head's kernel (fd_mlp_predict_*, FD_SLOT_MLP) */,
-                      FD_TIMING_GRAPH = 10 /* one fd_graph_step_*: every kernel of its chunks */ };
+                      FD_TIMING_GRAPH = 10 /* one fd_graph_step_*: every kernel of its chunks */,
+                      FD_TIMING_TEXT = 11 /* one fd_text_features_*: every kernel of its chunks */ };
 int fd_engine_set_timing(fd_engine* eng, int enable);
 /* Engine tuning knobs (for A/B measurement; defaults are the tuned choices):
      "forest_kernel": 0 auto, 1 force the 256-thread kernel, 2 force the 1024-thread tree-split kernel
@@ -832,6 +875,8 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    the compact 64-B rows: no vectors requested), "ensemble_single_launches" (fd_forest_predict batches scored by the
    fused kernel over one forest), "forest_sparse_launches" (launches of the sparse-layout forest kernel),
    "mlp_launches" (launches of the MLP head's kernel), "graph_steps" (fd_graph_step_* calls with n > 0),
+   "text_calls" (fd_text_features_device / _host calls with n > 0), "text_nonascii_rows" (rows those calls flagged
+   FD_TEXT_NONASCII; reading it waits for the engine stream),
    "pipelined_slot_stream_batches" (of those, with the slot pass on
    its own stream), "pipelined_host_ns" (host nanoseconds inside fd_score_batch_pipelined), "sharded_steps" (fd_sharded_step calls), "rccl_ops" (RCCL operations the exchanges issued: sends, receives,
    all-gathers) and "sharded_host_ns_<phase>" (host

@@ -11,6 +11,7 @@
 #include "fd_internal.h"
 #include "graph_row.h"
 #include "ingest_parse.h"
+#include "text_row.h"
 
 namespace fd {
 
@@ -351,6 +352,7 @@ int fd_engine_destroy(fd_engine* eng) {
   fd::windows_release(e);
   fd::sink_release(e);
   fd::graph_release(e);
+  fd::text_release(e);
   for (auto* b : {&e.route_blk, &e.route_blk_stream, &e.route_out, &e.route_err, &e.seq_buf, &e.seq_desc, &e.lstm.wpk, &e.lstm.wpk4, &e.lstm.bias,
                   &e.lstm.wout, &e.lstm.bout, &e.state.seq, &e.mlp.blob})
     b->release();
@@ -494,6 +496,10 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
     *value = (int64_t)e.mlp_total;
   } else if (k == "graph_steps") {  // fd_graph_step_* calls that appended transactions
     *value = (int64_t)e.graph.steps;
+  } else if (k == "text_calls") {  // fd_text_features_* calls with n > 0
+    *value = (int64_t)e.text.calls;
+  } else if (k == "text_nonascii_rows") {  // rows those calls flagged FD_TEXT_NONASCII (waits for the engine stream)
+    *value = fd::text_nonascii_rows(e);
   } else if (k == "latency_prebinned_batches") {  // latency pair launches that used the feature kernel's bins
     *value = (int64_t)e.prebin_total;
   } else if (k == "pipelined_split_batches") {  // of the compact ones: split rows (compact_vectors 2)
@@ -2015,6 +2021,61 @@ int fd_graph_features_host(const uint64_t* card_key, const int32_t* merchant, co
   FD_REQUIRE(card_key && merchant && amount_cents && out, FD_ERR_INVALID_ARG,
              "null card_key / merchant / amount_cents / output");
   fd::graph_features_stream_host(card_key, merchant, amount_cents, n, max_history, out);
+  FD_API_END
+}
+
+int fd_text_features_device(fd_engine* eng, const fd_text_batch* d, int64_t n, double* d_feat, uint8_t* d_patterns,
+                            uint8_t* d_status) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(d, FD_ERR_INVALID_ARG, "null text batch");
+  fd::text_features(e, d->bytes, d->off, n, d_feat, d_patterns, d_status);
+  FD_API_END
+}
+
+int fd_text_features_host(fd_engine* eng, const fd_text_batch* t, int64_t n, double* feat, uint8_t* patterns,
+                          uint8_t* status) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(t, FD_ERR_INVALID_ARG, "null text batch");
+  FD_REQUIRE(n >= 0 && n < (1ll << 31), FD_ERR_INVALID_ARG, "batch size out of range");
+  if (n == 0) return FD_OK;
+  FD_REQUIRE(t->off, FD_ERR_INVALID_ARG, "null text offsets");
+  FD_REQUIRE(fd::text_offsets_valid(t->off, n), FD_ERR_INVALID_ARG,
+             "text offsets must start at 0 and never decrease");
+  const int64_t total = t->off[4 * n];
+  FD_REQUIRE(total == 0 || t->bytes, FD_ERR_INVALID_ARG, "null text bytes");
+  const size_t off_bytes = ((size_t)(4 * n + 1) * 8 + 15) & ~(size_t)15;  // the bytes behind them stay 16-B aligned
+  e.stage_in.ensure(off_bytes + (size_t)total);
+  e.stage_out0.ensure((size_t)n * FD_TEXT_FEATURES * sizeof(double));
+  e.stage_out1.ensure((size_t)n * 2);
+  char* b = e.stage_in.as<char>();
+  FD_HIP(hipMemcpyAsync(b, t->off, (size_t)(4 * n + 1) * 8, hipMemcpyHostToDevice, e.stream));
+  if (total > 0) FD_HIP(hipMemcpyAsync(b + off_bytes, t->bytes, (size_t)total, hipMemcpyHostToDevice, e.stream));
+  uint8_t* d_pat = e.stage_out1.as<uint8_t>();
+  fd::text_features(e, reinterpret_cast<const uint8_t*>(b + off_bytes), reinterpret_cast<const int64_t*>(b), n,
+                    feat ? e.stage_out0.as<double>() : nullptr, patterns ? d_pat : nullptr,
+                    status ? d_pat + n : nullptr);
+  if (feat)
+    FD_HIP(hipMemcpyAsync(feat, e.stage_out0.ptr, (size_t)n * FD_TEXT_FEATURES * sizeof(double),
+                          hipMemcpyDeviceToHost, e.stream));
+  if (patterns) FD_HIP(hipMemcpyAsync(patterns, d_pat, (size_t)n, hipMemcpyDeviceToHost, e.stream));
+  if (status) FD_HIP(hipMemcpyAsync(status, d_pat + n, (size_t)n, hipMemcpyDeviceToHost, e.stream));
+  FD_HIP(hipStreamSynchronize(e.stream));
+  FD_API_END
+}
+
+int fd_text_features_ref_host(const uint8_t* bytes, const int64_t* off, int64_t n, double* feat, uint8_t* patterns,
+                              uint8_t* status) {
+  FD_API_BEGIN
+  FD_REQUIRE(n >= 0, FD_ERR_INVALID_ARG, "negative n");
+  if (n == 0) return FD_OK;
+  FD_REQUIRE(off, FD_ERR_INVALID_ARG, "null text offsets");
+  FD_REQUIRE(fd::text_offsets_valid(off, n), FD_ERR_INVALID_ARG, "text offsets must start at 0 and never decrease");
+  FD_REQUIRE(off[4 * n] == 0 || bytes, FD_ERR_INVALID_ARG, "null text bytes");
+  fd::text_features_rows_host(bytes, off, n, feat, patterns, status);
   FD_API_END
 }
 

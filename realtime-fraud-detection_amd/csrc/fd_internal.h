@@ -283,6 +283,15 @@ struct GraphState {
   unsigned long long steps = 0;  // counter "graph_steps"
 };
 
+// Text patterns and features (text.hip): per-row accumulators of one chunk, and the device-side counter behind
+// "text_nonascii_rows" (nothing is read back per call)
+constexpr int kTextChunk = 65536;  // rows per pass of the text kernels (the accumulators stay at chunk x 48 B)
+struct TextState {
+  DeviceBuffer acc;
+  DeviceBuffer count;
+  unsigned long long calls = 0;  // counter "text_calls"
+};
+
 // MLP head (mlp.hip): the packed model (header, per layer the A operands in the chained k order, padded biases)
 struct MlpModel {
   bool loaded = false;
@@ -571,6 +580,7 @@ struct Engine {
   MlpModel mlp;
   unsigned long long mlp_total = 0;  // counter "mlp_launches"
   GraphState graph;
+  TextState text;
   WindowState windows;
   IngestTables ingest;
   SinkState sink;
@@ -844,6 +854,11 @@ void graph_clear(Engine& e);
 void graph_release(Engine& e);
 void graph_info(Engine& e, int64_t* total, int64_t* held);
 void graph_step(Engine& e, const fd_txn_batch& t, int64_t n, double* d_out);  // device pointers, on e.stream
+// text.hip
+void text_release(Engine& e);
+int64_t text_nonascii_rows(Engine& e);  // waits for the engine stream
+void text_features(Engine& e, const uint8_t* d_bytes, const int64_t* d_off, int64_t n, double* d_feat,
+                   uint8_t* d_patterns, uint8_t* d_status);  // device pointers, on e.stream; outputs may be null
 // model_io.hip: the unchanged XGBoost 2.0.3 JSON model file, flattened (fdengine/forest.py semantics)
 struct XgbModel {
   int num_feature = 0;

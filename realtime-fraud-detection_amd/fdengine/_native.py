@@ -151,6 +151,10 @@ class fd_graph_params(C.Structure):
     _fields_ = [("max_history", C.c_int32)]
 
 
+class fd_text_batch(C.Structure):
+    _fields_ = [("bytes", C.c_void_p), ("off", C.c_void_p)]
+
+
 class fd_users(C.Structure):
     _fields_ = [("n", C.c_int64), ("key", C.c_void_p), ("avg_amount", C.c_void_p),
                 ("account_age_days", C.c_void_p), ("device_fp", C.c_void_p)]
@@ -174,6 +178,7 @@ FD_TIMING_INGEST = 7
 FD_TIMING_ENSEMBLE = 8
 FD_TIMING_MLP = 9
 FD_TIMING_GRAPH = 10
+FD_TIMING_TEXT = 11
 
 # JSON ingest codec (fd_ingest_out column order and dtypes)
 INGEST_FIELDS = (("card_key", "<u8"), ("ts_ms", "<i8"), ("amount_cents", "<i8"), ("merchant", "<i4"),
@@ -228,6 +233,17 @@ FD_SLOT_MLP = 65
 FD_GRAPH_FEATURES = 5
 GRAPH_COLUMNS = ("user_centrality", "merchant_centrality", "clustering_coefficient", "path_length_anomaly",
                  "community_anomaly")
+FD_TEXT_FIELDS = 4
+FD_TEXT_PATTERNS = 5
+FD_TEXT_FEATURES = 14
+FD_TEXT_NONASCII = 1
+TEXT_FIELDS = ("merchant_name", "description", "category", "location")
+TEXT_COLUMNS = ("merchant_name_length", "description_length", "total_text_length", "merchant_name_unique_chars",
+                "merchant_name_char_diversity", "numbers_in_merchant", "numbers_in_description", "total_numbers",
+                "special_chars_merchant", "special_chars_description", "total_special_chars", "merchant_word_count",
+                "description_word_count", "total_word_count")
+TEXT_PATTERNS = ("crypto_keywords", "gift_card_keywords", "urgent_language", "suspicious_merchant",
+                 "known_scam_patterns")
 FD_SEQ_INPUT = 16
 FD_MAX_SHARDS = 64
 FD_ROUTE_RECORD_BYTES = 48
@@ -300,6 +316,9 @@ SIGNATURES = {
     "fd_graph_step_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _vp]),
     "fd_graph_step_host": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _vp]),
     "fd_graph_features_host": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "fd_text_features_device": (C.c_int, [_vp, C.POINTER(fd_text_batch), _i64, _vp, _vp, _vp]),
+    "fd_text_features_host": (C.c_int, [_vp, C.POINTER(fd_text_batch), _i64, _vp, _vp, _vp]),
+    "fd_text_features_ref_host": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "fd_features_seq_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _vp, _vp, _vp]),
     "fd_shard_of_host": (C.c_int, [_vp, _i64, _i32, _vp]),
     "fd_route_partition_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _i32, _vp, _vp]),

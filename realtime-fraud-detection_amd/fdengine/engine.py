@@ -494,6 +494,34 @@ class FraudEngine:
         b = N.fd_txn_batch(**{f: int(ptrs[f]) for f in ("card_key", "merchant", "amount_cents")})
         N.call("fd_graph_step_device", self._h, C.byref(b), int(n), C.c_void_p(out_ptr) if out_ptr else None)
 
+    # ------------------------------------------------------------------ text patterns and features (text analyzer)
+    def text_features(self, data, off):
+        """Rows of four fields (fdengine._native.TEXT_FIELDS) as one byte blob (bytes or a uint8 array) and 4n + 1
+        offsets -> (f64 [n, 14] in TEXT_COLUMNS order, uint8 [n] pattern bits in TEXT_PATTERNS order, uint8 [n]
+        status). Rows with a non-ASCII byte have status FD_TEXT_NONASCII and zero outputs."""
+        blob = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) \
+            else np.ascontiguousarray(data, np.uint8)
+        off = np.ascontiguousarray(off, np.int64)
+        if off.ndim != 1 or len(off) % 4 != 1:
+            raise ValueError("text offsets must have 4 n + 1 entries")
+        n = len(off) // 4
+        if n and int(off[-1]) > len(blob):
+            raise ValueError("text offsets reach past the blob")
+        feat = np.empty((n, N.FD_TEXT_FEATURES), np.float64)
+        patterns = np.empty(n, np.uint8)
+        status = np.empty(n, np.uint8)
+        b = N.fd_text_batch(blob.ctypes.data if len(blob) else None, off.ctypes.data)
+        N.call("fd_text_features_host", self._h, C.byref(b), n, _ptr(feat), _ptr(patterns), _ptr(status))
+        return feat, patterns, status
+
+    def text_features_device(self, bytes_ptr: int, off_ptr: int, n: int, feat_ptr: int = 0, patterns_ptr: int = 0,
+                             status_ptr: int = 0) -> None:
+        """Device pointers (blob, int64 offsets; outputs f64 [n, 14], uint8 [n], uint8 [n], any of them 0 = not
+        wanted); on the engine stream, nothing read back."""
+        b = N.fd_text_batch(int(bytes_ptr) or None, int(off_ptr) or None)
+        N.call("fd_text_features_device", self._h, C.byref(b), int(n), *(C.c_void_p(p) if p else None
+                                                                        for p in (feat_ptr, patterns_ptr, status_ptr)))
+
     # ------------------------------------------------------------------ card-hash sharding (fdengine/sharding.py)
     def route_partition_device(self, txn_ptrs: dict, n: int, n_shards: int, records_ptr: int, counts_ptr: int) -> None:
         """Group one device-resident micro-batch by owner GPU: n records of FD_ROUTE_RECORD_BYTES at
