@@ -10,6 +10,7 @@
 #include "blend_row.h"
 #include "fd_internal.h"
 #include "graph_row.h"
+#include "host_stage.h"
 #include "ingest_parse.h"
 #include "text_row.h"
 
@@ -38,6 +39,7 @@ Engine::Timed* Engine::next_event_pair(int kind) {
 }  // namespace fd
 
 using fd::Engine;
+using fd::Stage;
 
 #define FD_API_BEGIN try {
 #define FD_API_END                    \
@@ -340,15 +342,9 @@ int fd_engine_destroy(fd_engine* eng) {
     f.b_thr.release();
     f.b_thr_off.release();
   }
-  e.stage_in.release();
-  e.stage_out0.release();
-  e.stage_out1.release();
-  e.stage_out2.release();
-  e.stage_out3.release();
+  e.stage.release();
   e.scratch_probs.release();
-  e.stage_ext.release();
   e.feat_vec.release();
-  e.feat_in.release();
   fd::windows_release(e);
   fd::sink_release(e);
   fd::graph_release(e);
@@ -398,9 +394,9 @@ int fd_engine_destroy(fd_engine* eng) {
     for (auto* b : {&P1.nodes[0], &P1.nodes[1], &P1.thr}) b->release();
   for (auto* b : {&e.ens.nodes[0], &e.ens.nodes[1], &e.ens.thr})
     b->release();
-  {  // ingest codec tables and staging
+  {  // ingest codec tables
     fd::IngestTables& t = e.ingest;
-    for (auto* b : {&t.mkeys, &t.mvals, &t.stage_bytes, &t.stage_offsets, &t.stage_out}) b->release();
+    for (auto* b : {&t.mkeys, &t.mvals}) b->release();
     for (int w = 0; w < 3; ++w) {
       t.vkeys[w].release();
       t.vvals[w].release();
@@ -928,21 +924,17 @@ int fd_forest_predict_host(fd_engine* eng, int slot, const float* X, int64_t n, 
   FD_REQUIRE(pf.loaded, FD_ERR_NOT_LOADED, "Model in slot " + std::to_string(slot) + " not loaded");
   FD_REQUIRE(n >= 0 && ld > 0 && X && prob, FD_ERR_INVALID_ARG, "bad arguments");
   if (n == 0) return FD_OK;
-  const size_t xb = (size_t)n * ld * sizeof(float);
-  e.stage_in.ensure(xb);
-  e.stage_out0.ensure((size_t)n * sizeof(double));
-  if (raw) e.stage_out1.ensure((size_t)n * sizeof(double));
-  if (leaf) e.stage_out2.ensure((size_t)n * pf.n_trees * sizeof(int32_t));
-  FD_HIP(hipMemcpyAsync(e.stage_in.ptr, X, xb, hipMemcpyHostToDevice, e.stream));
-  fd::launch_forest(e, pf, e.stage_in.as<float>(), n, ld, e.stage_out0.as<double>(),
-                    raw ? e.stage_out1.as<double>() : nullptr, leaf ? e.stage_out2.as<int32_t>() : nullptr);
-  FD_HIP(hipMemcpyAsync(prob, e.stage_out0.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  if (raw)
-    FD_HIP(hipMemcpyAsync(raw, e.stage_out1.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  if (leaf)
-    FD_HIP(hipMemcpyAsync(leaf, e.stage_out2.ptr, (size_t)n * pf.n_trees * sizeof(int32_t),
-                          hipMemcpyDeviceToHost, e.stream));
-  FD_HIP(hipStreamSynchronize(e.stream));
+  Stage st(e);
+  const float* dX;
+  double *dprob, *draw;
+  int32_t* dleaf;
+  st.in(dX, X, (size_t)n * ld);
+  st.out(dprob, prob, (size_t)n);
+  st.out(draw, raw, (size_t)n);
+  st.out(dleaf, leaf, (size_t)n * pf.n_trees);
+  st.upload();
+  fd::launch_forest(e, pf, dX, n, ld, dprob, draw, dleaf);
+  st.download();
   FD_API_END
 }
 
@@ -1008,34 +1000,19 @@ int fd_features_host(fd_engine* eng, const fd_txn_batch* txns, int64_t n, float*
   Engine& e = E(eng);
   FD_REQUIRE(txns && vectors && n >= 0, FD_ERR_INVALID_ARG, "bad arguments");
   if (n == 0) return FD_OK;
-  // stage the SoA columns in one device buffer (8-byte aligned segments)
-  const size_t seg8 = (size_t)n * 8, seg4 = ((size_t)n * 4 + 7) / 8 * 8, seg1 = ((size_t)n + 7) / 8 * 8;
-  const size_t total = 4 * seg8 + seg4 + 3 * seg1;
-  e.feat_in.ensure(total);
-  char* b = e.feat_in.as<char>();
+  FD_REQUIRE(txns->card_key && txns->ts_ms && txns->amount_cents && txns->device_fp && txns->merchant &&
+                 txns->ip_class && txns->hour && txns->weekend,
+             FD_ERR_INVALID_ARG, "incomplete transaction batch");
+  Stage st(e);
   fd_txn_batch d{};
-  size_t off = 0;
-  auto put = [&](const void* src, size_t bytes, size_t seg) -> void* {
-    FD_REQUIRE(src, FD_ERR_INVALID_ARG, "incomplete transaction batch");
-    void* dst = b + off;
-    FD_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, e.stream));
-    off += seg;
-    return dst;
-  };
-  d.card_key = (const uint64_t*)put(txns->card_key, n * 8, seg8);
-  d.ts_ms = (const int64_t*)put(txns->ts_ms, n * 8, seg8);
-  d.amount_cents = (const int64_t*)put(txns->amount_cents, n * 8, seg8);
-  d.device_fp = (const uint64_t*)put(txns->device_fp, n * 8, seg8);
-  d.merchant = (const int32_t*)put(txns->merchant, n * 4, seg4);
-  d.ip_class = (const uint8_t*)put(txns->ip_class, n, seg1);
-  d.hour = (const uint8_t*)put(txns->hour, n, seg1);
-  d.weekend = (const uint8_t*)put(txns->weekend, n, seg1);
-  e.feat_vec.ensure((size_t)n * FD_VECTOR_WIDTH * 4 + (raw ? (size_t)n * FD_RAW_FEATURES * 8 : 0));
-  float* dv = e.feat_vec.as<float>();
-  double* dr = raw ? reinterpret_cast<double*>(e.feat_vec.as<char>() + (size_t)n * FD_VECTOR_WIDTH * 4) : nullptr;
+  float* dv;
+  double* dr;
+  stage_txns(st, d, *txns, n, fd::kTxnAll);
+  st.out(dv, vectors, (size_t)n * FD_VECTOR_WIDTH);
+  st.out(dr, raw, (size_t)n * FD_RAW_FEATURES);
+  st.upload();
   fd::launch_features(e, d, n, dv, dr);
-  FD_HIP(hipMemcpyAsync(vectors, dv, (size_t)n * FD_VECTOR_WIDTH * 4, hipMemcpyDeviceToHost, e.stream));
-  if (raw) FD_HIP(hipMemcpyAsync(raw, dr, (size_t)n * FD_RAW_FEATURES * 8, hipMemcpyDeviceToHost, e.stream));
+  st.download(/*wait=*/false);
   fd::features_check(e);  // synchronises
   FD_API_END
 }
@@ -1064,33 +1041,25 @@ int fd_score_matrix_host(fd_engine* eng, const fd_blend_params* params, const in
   FD_REQUIRE(params->n_models > 0 && params->n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, "n_models out of range");
   if (n == 0) return FD_OK;
   const int M = params->n_models;
-  const size_t xb = (size_t)n * ld * sizeof(float);
-  e.stage_in.ensure(xb);
-  e.scratch_probs.ensure((size_t)n * M * sizeof(double));
-  e.stage_out0.ensure((size_t)n * sizeof(double));
-  e.stage_out1.ensure((size_t)n * sizeof(double));
-  e.stage_out2.ensure((size_t)n);
-  e.stage_out3.ensure((size_t)n);
-  FD_HIP(hipMemcpyAsync(e.stage_in.ptr, X, xb, hipMemcpyHostToDevice, e.stream));
-  double* dMP = e.scratch_probs.as<double>();
+  Stage st(e);
+  const float* dX;
   const double* dext[FD_MAX_MODELS] = {};
-  for (int m = 0; m < M; ++m) {
+  double *dMP, *dfp, *dconf;
+  uint8_t *ddec, *drisk;
+  st.in(dX, X, (size_t)n * ld);
+  for (int m = 0; m < M; ++m) {  // the external columns; score_matrix copies each into its place in the matrix
     if (slots[m] >= 0 || (present && !present[m])) continue;
     FD_REQUIRE(ext_probs && ext_probs[m], FD_ERR_INVALID_ARG, "model without slot needs an external probability column");
-    FD_HIP(hipMemcpyAsync(dMP + (size_t)m * n, ext_probs[m], (size_t)n * sizeof(double), hipMemcpyHostToDevice,
-                          e.stream));
-    dext[m] = dMP + (size_t)m * n;
+    st.in(dext[m], ext_probs[m], (size_t)n);
   }
-  score_matrix(e, *params, slots, dext, present, e.stage_in.as<float>(), n, ld, dMP, e.stage_out0.as<double>(),
-               e.stage_out1.as<double>(), e.stage_out2.as<uint8_t>(), e.stage_out3.as<uint8_t>());
-  if (model_probs)
-    FD_HIP(hipMemcpyAsync(model_probs, dMP, (size_t)n * M * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  FD_HIP(hipMemcpyAsync(fraud_prob, e.stage_out0.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  if (confidence)
-    FD_HIP(hipMemcpyAsync(confidence, e.stage_out1.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  if (decision) FD_HIP(hipMemcpyAsync(decision, e.stage_out2.ptr, (size_t)n, hipMemcpyDeviceToHost, e.stream));
-  if (risk) FD_HIP(hipMemcpyAsync(risk, e.stage_out3.ptr, (size_t)n, hipMemcpyDeviceToHost, e.stream));
-  FD_HIP(hipStreamSynchronize(e.stream));
+  st.out(dMP, model_probs, (size_t)n * M);  // absent: score_matrix keeps the matrix in its own scratch
+  st.out(dfp, fraud_prob, (size_t)n);
+  st.out(dconf, confidence, (size_t)n);
+  st.out(ddec, decision, (size_t)n);
+  st.out(drisk, risk, (size_t)n);
+  st.upload();
+  score_matrix(e, *params, slots, dext, present, dX, n, ld, dMP, dfp, dconf, ddec, drisk);
+  st.download();
   FD_API_END
 }
 
@@ -1551,32 +1520,13 @@ int fd_windows_step_host(fd_engine* eng, const fd_txn_batch* txns, const fd_wind
   if (n > 0) {
     FD_REQUIRE(txns->card_key && txns->ts_ms && txns->amount_cents && txns->merchant, FD_ERR_INVALID_ARG,
                "batch needs card_key, ts_ms, amount_cents and merchant");
-    const fd_window_inputs none_in{};
-    const fd_window_inputs& hi = in ? *in : none_in;
-    // staging layout: key | ts | cents | fraud_score (8 B each) | merchant (4 B) | pm | fraud (1 B each)
-    const size_t n8 = (size_t)n * 8, n4 = (size_t)n * 4;
-    e.windows.stage.ensure(4 * n8 + n4 + 2 * (size_t)n + 64);
-    char* d = e.windows.stage.as<char>();
-    FD_HIP(hipMemcpyAsync(d, txns->card_key, n8, hipMemcpyHostToDevice, e.stream));
-    FD_HIP(hipMemcpyAsync(d + n8, txns->ts_ms, n8, hipMemcpyHostToDevice, e.stream));
-    FD_HIP(hipMemcpyAsync(d + 2 * n8, txns->amount_cents, n8, hipMemcpyHostToDevice, e.stream));
-    FD_HIP(hipMemcpyAsync(d + 4 * n8, txns->merchant, n4, hipMemcpyHostToDevice, e.stream));
-    dt.card_key = reinterpret_cast<const uint64_t*>(d);
-    dt.ts_ms = reinterpret_cast<const int64_t*>(d + n8);
-    dt.amount_cents = reinterpret_cast<const int64_t*>(d + 2 * n8);
-    dt.merchant = reinterpret_cast<const int32_t*>(d + 4 * n8);
-    if (hi.fraud_score) {
-      FD_HIP(hipMemcpyAsync(d + 3 * n8, hi.fraud_score, n8, hipMemcpyHostToDevice, e.stream));
-      di.fraud_score = reinterpret_cast<const double*>(d + 3 * n8);
-    }
-    if (hi.payment_method) {
-      FD_HIP(hipMemcpyAsync(d + 4 * n8 + n4, hi.payment_method, (size_t)n, hipMemcpyHostToDevice, e.stream));
-      di.payment_method = reinterpret_cast<const uint8_t*>(d + 4 * n8 + n4);
-    }
-    if (hi.is_fraud) {
-      FD_HIP(hipMemcpyAsync(d + 4 * n8 + n4 + n, hi.is_fraud, (size_t)n, hipMemcpyHostToDevice, e.stream));
-      di.is_fraud = reinterpret_cast<const uint8_t*>(d + 4 * n8 + n4 + n);
-    }
+    const fd_window_inputs hi = in ? *in : fd_window_inputs{};
+    Stage st(e);
+    stage_txns(st, dt, *txns, n, fd::kTxnKey | fd::kTxnTs | fd::kTxnCents | fd::kTxnMerchant);
+    st.in(di.payment_method, hi.payment_method, (size_t)n);
+    st.in(di.is_fraud, hi.is_fraud, (size_t)n);
+    st.in(di.fraud_score, hi.fraud_score, (size_t)n);
+    st.upload();
   }
   fd::windows_step(e, dt, di, n, flush != 0, user_out, user_cap, n_user, merchant_out, merchant_cap, n_merchant);
   FD_API_END
@@ -1634,30 +1584,14 @@ int fd_sink_update_host(fd_engine* eng, const fd_txn_batch* txns, const fd_windo
   if (n == 0) return FD_OK;
   FD_REQUIRE(txns->card_key && txns->ts_ms && txns->amount_cents && txns->merchant, FD_ERR_INVALID_ARG,
              "batch needs card_key, ts_ms, amount_cents and merchant");
-  const size_t nn = (size_t)n;
-  const size_t fo = ((nn * 4 + 15) & ~(size_t)15), so = fo + ((nn + 15) & ~(size_t)15);
-  e.stage_in.ensure(nn * 24 + so + nn * 8 + 64);
-  char* b = e.stage_in.as<char>();
-  FD_HIP(hipMemcpyAsync(b, txns->card_key, nn * 8, hipMemcpyHostToDevice, e.stream));
-  FD_HIP(hipMemcpyAsync(b + nn * 8, txns->ts_ms, nn * 8, hipMemcpyHostToDevice, e.stream));
-  FD_HIP(hipMemcpyAsync(b + nn * 16, txns->amount_cents, nn * 8, hipMemcpyHostToDevice, e.stream));
-  char* x = b + nn * 24;
-  FD_HIP(hipMemcpyAsync(x, txns->merchant, nn * 4, hipMemcpyHostToDevice, e.stream));
-  fd_window_inputs din{nullptr, nullptr, nullptr};
-  if (in && in->is_fraud) {
-    FD_HIP(hipMemcpyAsync(x + fo, in->is_fraud, nn, hipMemcpyHostToDevice, e.stream));
-    din.is_fraud = reinterpret_cast<const uint8_t*>(x + fo);
-  }
-  if (in && in->fraud_score) {
-    FD_HIP(hipMemcpyAsync(x + so, in->fraud_score, nn * 8, hipMemcpyHostToDevice, e.stream));
-    din.fraud_score = reinterpret_cast<const double*>(x + so);
-  }
+  Stage st(e);
   fd_txn_batch d{};
-  d.card_key = reinterpret_cast<const uint64_t*>(b);
-  d.ts_ms = reinterpret_cast<const int64_t*>(b + nn * 8);
-  d.amount_cents = reinterpret_cast<const int64_t*>(b + nn * 16);
-  d.merchant = reinterpret_cast<const int32_t*>(x);
-  fd::sink_update(e, d, din, n);
+  fd_window_inputs din{};  // (the sink does not read payment_method)
+  stage_txns(st, d, *txns, n, fd::kTxnKey | fd::kTxnTs | fd::kTxnCents | fd::kTxnMerchant);
+  st.in(din.is_fraud, in ? in->is_fraud : nullptr, (size_t)n);
+  st.in(din.fraud_score, in ? in->fraud_score : nullptr, (size_t)n);
+  st.upload();
+  fd::sink_update(e, d, din, n);  // no wait here: the next call on e.stream is ordered behind it
   FD_API_END
 }
 
@@ -1720,53 +1654,37 @@ int fd_ingest_json_host(fd_engine* eng, const uint8_t* bytes, const int64_t* off
   if (n == 0) return FD_OK;
   FD_REQUIRE(offsets[0] == 0 && offsets[n] >= 0, FD_ERR_INVALID_ARG, "offsets must start at 0");
   const size_t nb = (size_t)offsets[n];
-  fd::IngestTables& t = e.ingest;
-  t.stage_bytes.ensure(std::max<size_t>(nb, 16));
-  t.stage_offsets.ensure((size_t)(n + 1) * 8);
-  if (nb) FD_HIP(hipMemcpyAsync(t.stage_bytes.ptr, bytes, nb, hipMemcpyHostToDevice, e.stream));
-  FD_HIP(hipMemcpyAsync(t.stage_offsets.ptr, offsets, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, e.stream));
-  // device columns: one staging block, 8-byte columns first
-  struct Col { void* host; size_t w; };
-  const Col cols[] = {{out->card_key, 8}, {out->ts_ms, 8}, {out->amount_cents, 8}, {out->device_fp, 8},
-                      {out->geo_lat, 8}, {out->geo_lon, 8}, {out->merchant_lat, 8}, {out->merchant_lon, 8},
-                      {out->fraud_score, 8}, {out->txn_hash, 8}, {out->merchant, 4}, {out->ip_class, 1},
-                      {out->hour, 1}, {out->weekend, 1}, {out->payment_method, 1}, {out->transaction_type, 1},
-                      {out->card_type, 1}, {out->user_agent_flag, 1}, {out->is_fraud, 1}, {out->status, 1}};
-  constexpr int NC = sizeof(cols) / sizeof(cols[0]);
-  size_t offs[NC], total = 0;
-  for (int c = 0; c < NC; ++c) {
-    offs[c] = total;
-    if (cols[c].host) total += ((size_t)n * cols[c].w + 15) & ~(size_t)15;
-  }
-  t.stage_out.ensure(std::max<size_t>(total, 16));
-  char* base = t.stage_out.as<char>();
-  auto dev = [&](int c) -> void* { return cols[c].host ? base + offs[c] : nullptr; };
+  Stage st(e);
+  const uint8_t* d_bytes;
+  const int64_t* d_offsets;
+  static const uint8_t no_bytes = 0;  // nb == 0: the kernel still gets a byte pointer, and `bytes` may be null
+  st.in(d_bytes, nb ? bytes : &no_bytes, nb);
+  st.in(d_offsets, offsets, (size_t)n + 1);
   fd_ingest_out d{};
-  d.card_key = (uint64_t*)dev(0);
-  d.ts_ms = (int64_t*)dev(1);
-  d.amount_cents = (int64_t*)dev(2);
-  d.device_fp = (uint64_t*)dev(3);
-  d.geo_lat = (double*)dev(4);
-  d.geo_lon = (double*)dev(5);
-  d.merchant_lat = (double*)dev(6);
-  d.merchant_lon = (double*)dev(7);
-  d.fraud_score = (double*)dev(8);
-  d.txn_hash = (uint64_t*)dev(9);
-  d.merchant = (int32_t*)dev(10);
-  d.ip_class = (uint8_t*)dev(11);
-  d.hour = (uint8_t*)dev(12);
-  d.weekend = (uint8_t*)dev(13);
-  d.payment_method = (uint8_t*)dev(14);
-  d.transaction_type = (uint8_t*)dev(15);
-  d.card_type = (uint8_t*)dev(16);
-  d.user_agent_flag = (uint8_t*)dev(17);
-  d.is_fraud = (uint8_t*)dev(18);
-  d.status = (uint8_t*)dev(19);
-  fd::launch_ingest(e, t.stage_bytes.as<const uint8_t>(), t.stage_offsets.as<const int64_t>(), n, d);
-  for (int c = 0; c < NC; ++c)
-    if (cols[c].host)
-      FD_HIP(hipMemcpyAsync(cols[c].host, base + offs[c], (size_t)n * cols[c].w, hipMemcpyDeviceToHost, e.stream));
-  FD_HIP(hipStreamSynchronize(e.stream));
+  auto col = [&](auto member) { st.out(d.*member, out->*member, (size_t)n); };
+  col(&fd_ingest_out::card_key);
+  col(&fd_ingest_out::ts_ms);
+  col(&fd_ingest_out::amount_cents);
+  col(&fd_ingest_out::merchant);
+  col(&fd_ingest_out::device_fp);
+  col(&fd_ingest_out::ip_class);
+  col(&fd_ingest_out::hour);
+  col(&fd_ingest_out::weekend);
+  col(&fd_ingest_out::geo_lat);
+  col(&fd_ingest_out::geo_lon);
+  col(&fd_ingest_out::merchant_lat);
+  col(&fd_ingest_out::merchant_lon);
+  col(&fd_ingest_out::payment_method);
+  col(&fd_ingest_out::transaction_type);
+  col(&fd_ingest_out::card_type);
+  col(&fd_ingest_out::user_agent_flag);
+  col(&fd_ingest_out::fraud_score);
+  col(&fd_ingest_out::is_fraud);
+  col(&fd_ingest_out::txn_hash);
+  col(&fd_ingest_out::status);
+  st.upload();
+  fd::launch_ingest(e, d_bytes, d_offsets, n, d);
+  st.download();
   FD_API_END
 }
 
@@ -1860,13 +1778,14 @@ int fd_lstm_predict_host(fd_engine* eng, const float* seq, int64_t n, int32_t T,
   FD_REQUIRE(n >= 0 && T >= 1 && T <= FD_MAX_SEQ_LEN, FD_ERR_INVALID_ARG, "bad arguments");
   if (n == 0) return FD_OK;
   FD_REQUIRE(seq && prob, FD_ERR_INVALID_ARG, "null sequence / output");
-  const size_t sb = (size_t)n * T * fd::kSeqInput * sizeof(float);
-  e.stage_in.ensure(sb);
-  e.stage_out0.ensure((size_t)n * sizeof(double));
-  FD_HIP(hipMemcpyAsync(e.stage_in.ptr, seq, sb, hipMemcpyHostToDevice, e.stream));
-  fd::launch_lstm(e, e.stream, e.stage_in.as<float>(), n, T, e.stage_out0.as<double>());
-  FD_HIP(hipMemcpyAsync(prob, e.stage_out0.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  FD_HIP(hipStreamSynchronize(e.stream));
+  Stage st(e);
+  const float* dseq;
+  double* dprob;
+  st.in(dseq, seq, (size_t)n * T * fd::kSeqInput);
+  st.out(dprob, prob, (size_t)n);
+  st.upload();
+  fd::launch_lstm(e, e.stream, dseq, n, T, dprob);
+  st.download();
   FD_API_END
 }
 
@@ -1938,13 +1857,14 @@ int fd_mlp_predict_host(fd_engine* eng, const float* X, int64_t n, int32_t ld, d
              "row stride " + std::to_string(ld) + " is below the MLP's in_dim " + std::to_string(e.mlp.dims[0]));
   if (n == 0) return FD_OK;
   FD_REQUIRE(X && prob, FD_ERR_INVALID_ARG, "null vectors / output");
-  const size_t xb = (size_t)n * ld * sizeof(float);
-  e.stage_in.ensure(xb);
-  e.stage_out0.ensure((size_t)n * sizeof(double));
-  FD_HIP(hipMemcpyAsync(e.stage_in.ptr, X, xb, hipMemcpyHostToDevice, e.stream));
-  fd::launch_mlp(e, e.stream, e.stage_in.as<float>(), n, ld, e.stage_out0.as<double>());
-  FD_HIP(hipMemcpyAsync(prob, e.stage_out0.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  FD_HIP(hipStreamSynchronize(e.stream));
+  Stage st(e);
+  const float* dX;
+  double* dprob;
+  st.in(dX, X, (size_t)n * ld);
+  st.out(dprob, prob, (size_t)n);
+  st.upload();
+  fd::launch_mlp(e, e.stream, dX, n, ld, dprob);
+  st.download();
   FD_API_END
 }
 
@@ -1993,21 +1913,14 @@ int fd_graph_step_host(fd_engine* eng, const fd_txn_batch* txns, int64_t n, doub
   if (n == 0) return FD_OK;
   FD_REQUIRE(txns->card_key && txns->merchant && txns->amount_cents && out, FD_ERR_INVALID_ARG,
              "null card_key / merchant / amount_cents / output");
-  const size_t seg8 = (size_t)n * 8;
-  e.stage_in.ensure(2 * seg8 + (size_t)n * 4);
-  e.stage_out0.ensure((size_t)n * FD_GRAPH_FEATURES * sizeof(double));
-  char* b = e.stage_in.as<char>();
+  Stage st(e);
   fd_txn_batch d{};
-  FD_HIP(hipMemcpyAsync(b, txns->card_key, seg8, hipMemcpyHostToDevice, e.stream));
-  FD_HIP(hipMemcpyAsync(b + seg8, txns->amount_cents, seg8, hipMemcpyHostToDevice, e.stream));
-  FD_HIP(hipMemcpyAsync(b + 2 * seg8, txns->merchant, (size_t)n * 4, hipMemcpyHostToDevice, e.stream));
-  d.card_key = reinterpret_cast<const uint64_t*>(b);
-  d.amount_cents = reinterpret_cast<const int64_t*>(b + seg8);
-  d.merchant = reinterpret_cast<const int32_t*>(b + 2 * seg8);
-  fd::graph_step(e, d, n, e.stage_out0.as<double>());
-  FD_HIP(hipMemcpyAsync(out, e.stage_out0.ptr, (size_t)n * FD_GRAPH_FEATURES * sizeof(double), hipMemcpyDeviceToHost,
-                        e.stream));
-  FD_HIP(hipStreamSynchronize(e.stream));
+  double* dout;
+  stage_txns(st, d, *txns, n, fd::kTxnKey | fd::kTxnCents | fd::kTxnMerchant);
+  st.out(dout, out, (size_t)n * FD_GRAPH_FEATURES);
+  st.upload();
+  fd::graph_step(e, d, n, dout);
+  st.download();
   FD_API_END
 }
 
@@ -2047,23 +1960,18 @@ int fd_text_features_host(fd_engine* eng, const fd_text_batch* t, int64_t n, dou
              "text offsets must start at 0 and never decrease");
   const int64_t total = t->off[4 * n];
   FD_REQUIRE(total == 0 || t->bytes, FD_ERR_INVALID_ARG, "null text bytes");
-  const size_t off_bytes = ((size_t)(4 * n + 1) * 8 + 15) & ~(size_t)15;  // the bytes behind them stay 16-B aligned
-  e.stage_in.ensure(off_bytes + (size_t)total);
-  e.stage_out0.ensure((size_t)n * FD_TEXT_FEATURES * sizeof(double));
-  e.stage_out1.ensure((size_t)n * 2);
-  char* b = e.stage_in.as<char>();
-  FD_HIP(hipMemcpyAsync(b, t->off, (size_t)(4 * n + 1) * 8, hipMemcpyHostToDevice, e.stream));
-  if (total > 0) FD_HIP(hipMemcpyAsync(b + off_bytes, t->bytes, (size_t)total, hipMemcpyHostToDevice, e.stream));
-  uint8_t* d_pat = e.stage_out1.as<uint8_t>();
-  fd::text_features(e, reinterpret_cast<const uint8_t*>(b + off_bytes), reinterpret_cast<const int64_t*>(b), n,
-                    feat ? e.stage_out0.as<double>() : nullptr, patterns ? d_pat : nullptr,
-                    status ? d_pat + n : nullptr);
-  if (feat)
-    FD_HIP(hipMemcpyAsync(feat, e.stage_out0.ptr, (size_t)n * FD_TEXT_FEATURES * sizeof(double),
-                          hipMemcpyDeviceToHost, e.stream));
-  if (patterns) FD_HIP(hipMemcpyAsync(patterns, d_pat, (size_t)n, hipMemcpyDeviceToHost, e.stream));
-  if (status) FD_HIP(hipMemcpyAsync(status, d_pat + n, (size_t)n, hipMemcpyDeviceToHost, e.stream));
-  FD_HIP(hipStreamSynchronize(e.stream));
+  Stage st(e);
+  fd_text_batch d{};
+  double* dfeat;
+  uint8_t *dpat, *dstatus;
+  st.in(d.off, t->off, (size_t)(4 * n + 1));
+  st.in(d.bytes, t->bytes, (size_t)total);
+  st.out(dfeat, feat, (size_t)n * FD_TEXT_FEATURES);
+  st.out(dpat, patterns, (size_t)n);
+  st.out(dstatus, status, (size_t)n);
+  st.upload();
+  fd::text_features(e, d.bytes, d.off, n, dfeat, dpat, dstatus);
+  st.download();
   FD_API_END
 }
 
@@ -2195,28 +2103,22 @@ int fd_blend_host(fd_engine* eng, const fd_blend_params* params, int64_t n, cons
              "n_models out of range");
   if (n == 0) return FD_OK;
   const int M = params->n_models;
-  // stage_in holds the M probability columns; outputs in stage_out0..3
-  e.stage_in.ensure((size_t)n * sizeof(double) * (M > 0 ? M : 1));
-  e.stage_out0.ensure((size_t)n * sizeof(double));
-  e.stage_out1.ensure((size_t)n * sizeof(double));
-  e.stage_out2.ensure((size_t)n);
-  e.stage_out3.ensure((size_t)n);
+  Stage st(e);
   const double* dcols[FD_MAX_MODELS] = {};
-  for (int m = 0; m < M; ++m) {
-    double* col = e.stage_in.as<double>() + (size_t)m * n;
-    dcols[m] = col;
+  double *dfp, *dconf;
+  uint8_t *ddec, *drisk;
+  for (int m = 0; m < M; ++m) {  // (an absent model's column stays null: launch_blend skips it)
     if (present && !present[m]) continue;
     FD_REQUIRE(probs[m], FD_ERR_INVALID_ARG, "null probability column");
-    FD_HIP(hipMemcpyAsync(col, probs[m], (size_t)n * sizeof(double), hipMemcpyHostToDevice, e.stream));
+    st.in(dcols[m], probs[m], (size_t)n);
   }
-  fd::launch_blend(e, *params, n, dcols, present, e.stage_out0.as<double>(), e.stage_out1.as<double>(),
-                   e.stage_out2.as<uint8_t>(), e.stage_out3.as<uint8_t>());
-  FD_HIP(hipMemcpyAsync(fraud_prob, e.stage_out0.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  if (confidence)
-    FD_HIP(hipMemcpyAsync(confidence, e.stage_out1.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  if (decision) FD_HIP(hipMemcpyAsync(decision, e.stage_out2.ptr, (size_t)n, hipMemcpyDeviceToHost, e.stream));
-  if (risk) FD_HIP(hipMemcpyAsync(risk, e.stage_out3.ptr, (size_t)n, hipMemcpyDeviceToHost, e.stream));
-  FD_HIP(hipStreamSynchronize(e.stream));
+  st.out(dfp, fraud_prob, (size_t)n);
+  st.out(dconf, confidence, (size_t)n);
+  st.out(ddec, decision, (size_t)n);
+  st.out(drisk, risk, (size_t)n);
+  st.upload();
+  fd::launch_blend(e, *params, n, dcols, present, dfp, dconf, ddec, drisk);
+  st.download();
   FD_API_END
 }
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "fdengine.h"
+#include "key_hash.h"
 
 namespace fd {
 
@@ -367,13 +368,7 @@ struct CardPages {
 // header (snapshots and occupancy read it there). Returns the slot, -1 when the table is full.
 FD_CARD_SLOT_QUAL long long card_slot(unsigned long long* keys, CardPages pg, long long mask, unsigned long long key) {
   if (key == 0ull) key = 1ull;  // 0 marks an empty slot
-  unsigned long long m = key;
-  m ^= m >> 33;
-  m *= 0xff51afd7ed558ccdULL;
-  m ^= m >> 33;
-  m *= 0xc4ceb9fe1a85ec53ULL;
-  m ^= m >> 33;
-  long long h = (long long)(m & (unsigned long long)mask);
+  long long h = (long long)(fmix64(key) & (unsigned long long)mask);
   if (mask >= 7) {
     long long g = h & ~7ll;
     int j0 = (int)(h & 7);
@@ -469,7 +464,7 @@ struct WindowState {
   DeviceBuffer ulog[2], mlog[2];
   int ucur = 0, mcur = 0;
   int64_t ucount = 0, mcount = 0;
-  DeviceBuffer keys, vals, sort_tmp, uout, mout, scalars, stage;
+  DeviceBuffer keys, vals, sort_tmp, uout, mout, scalars;
 };
 
 // RedisTransactionSink bucket aggregates (sink.hip)
@@ -485,7 +480,6 @@ struct IngestTables {
   unsigned long long mmask = 0, vmask[3] = {0, 0, 0};
   bool mloaded = false, vloaded[3] = {false, false, false};
   int stop_after = 0;  // diagnostics option "ingest_stop_after"
-  DeviceBuffer stage_bytes, stage_offsets, stage_out;  // host-API staging
 };
 
 // the engine's own RCCL communicators and buffers for the sharded step (comm.hip, fd_sharded_step in engine.hip);
@@ -590,7 +584,7 @@ struct Engine {
   hipEvent_t join2_ev = nullptr;
   DeviceBuffer seq_buf;                        // per-txn LSTM input sequences of the fused path
   DeviceBuffer seq_desc;                       // latency path: per-txn sequence descriptors (kSeqMaterialized)
-  DeviceBuffer feat_vec, feat_in, feat_ext;  // host-API / fused-pipeline staging for features
+  DeviceBuffer feat_vec, feat_ext;  // feature vectors of the scoring entry points / extended-feature scratch
   // fd_score_batch_pipelined (engine.hip): features and scoring of batch i on pipe_stream[i & 1] (no cross-stream
   // wait between a batch's features and its forests; batch i-1's features waited for by event); vectors / LSTM
   // sequences double-buffered by batch parity
@@ -656,9 +650,8 @@ struct Engine {
                                 // nobody asked for vectors: 0 the 64-wide vector, 1 compact 64-B rows, 2 split rows
                                 // (card-independent half from the slot pass; engine.hip, features.hip Prep32)
   int stream_prio = 3;    // option "stream_priority": the pipeline / forward streams' HIP priorities (engine.hip)
-  // host-API staging
-  DeviceBuffer stage_in, stage_out0, stage_out1, stage_out2, stage_out3;
-  DeviceBuffer scratch_probs, stage_ext;  // score_matrix per-model columns / staged external columns
+  DeviceBuffer stage;          // the host (`_host`) entry points' staged inputs and outputs (engine.hip Stage)
+  DeviceBuffer scratch_probs;  // score_matrix per-model columns
   DeviceBuffer route_blk, route_out, route_err;  // card-hash routing scratch (route.hip)
   DeviceBuffer route_blk_stream;                 // fd_route_partition_stream's block counts (its own stream)
   ShardComm comm;                                // card-hash sharding over RCCL (comm.hip)

@@ -73,16 +73,6 @@ struct Merchant {
   double mult;
 };
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdULL;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ULL;
-  k ^= k >> 33;
-  return k;
-}
-
-
 __global__ void __launch_bounds__(256) users_load_kernel(CardPages P, unsigned long long* K, long long mask, int64_t n,
                                                          const unsigned long long* key, const double* avg,
                                                          const int* age, const unsigned long long* dfp,
@@ -817,7 +807,7 @@ __device__ __forceinline__ Prep fetch_prep(const BucketArgs& a, int64_t i) {
 
 // a card's bucket in gather mode: every transaction of a card in one bucket, buckets filled evenly
 __device__ __forceinline__ unsigned gather_bucket(unsigned long long key, unsigned nbm) {
-  return (unsigned)(mix64(key ^ 0x9E3779B97F4A7C15ull) >> 32) & nbm;
+  return (unsigned)(fmix64(key ^ 0x9E3779B97F4A7C15ull) >> 32) & nbm;
 }
 
 // The thread that takes bucket position pos (mod kBT): with `spread`, consecutive positions go to different waves, so
@@ -1466,7 +1456,7 @@ __global__ void __launch_bounds__(kBT) feat_bucket_lean_kernel(BucketArgs a, Buc
     if (hashed) {
       if (t < (int)m) {
         const unsigned s = (unsigned)(skeys[t] >> 32);
-        unsigned h = (unsigned)(mix64(s) >> 32) & (kHashCap - 1);
+        unsigned h = (unsigned)(fmix64(s) >> 32) & (kHashCap - 1);
         unsigned old;
         for (;;) {
           old = atomicCAS(&hslot[h], kHashEmpty, s);

@@ -668,7 +668,7 @@ struct Table {  // open addressing: hash -> value (key 0 = empty)
 __device__ __forceinline__ int table_find(const Table& t, uint64_t h, int miss) {
   if (!t.keys) return miss;
   if (h == 0) h = 1;
-  unsigned long long s = fmix64_hd(h ^ 0x9E3779B97F4A7C15ull) & t.mask;
+  unsigned long long s = fmix64(h ^ 0x9E3779B97F4A7C15ull) & t.mask;
   for (unsigned long long p = 0; p <= t.mask; ++p) {
     const unsigned long long k = t.keys[s];
     if (k == h) return t.vals[s];
@@ -1371,7 +1371,7 @@ void build_table(DeviceBuffer& keys, DeviceBuffer& vals, unsigned long long* mas
     FD_REQUIRE(offsets[i + 1] >= offsets[i], FD_ERR_INVALID_ARG, "vocabulary offsets must be non-decreasing");
     uint64_t h = hash_bytes(bytes + offsets[i], offsets[i + 1] - offsets[i]);
     if (h == 0) h = 1;
-    uint64_t s = fmix64_hd(h ^ 0x9E3779B97F4A7C15ull) & (cap - 1);
+    uint64_t s = fmix64(h ^ 0x9E3779B97F4A7C15ull) & (cap - 1);
     while (k[s] != 0ull && k[s] != h) s = (s + 1) & (cap - 1);
     if (k[s] == h) continue;  // duplicate string: the first position keeps its index
     k[s] = h;

@@ -12,13 +12,8 @@
 
 #include <cstdint>
 
+#include "key_hash.h"
 #include "pow5_table.h"
-
-#if defined(__HIPCC__)
-#define FD_HD __host__ __device__ __forceinline__
-#else
-#define FD_HD inline
-#endif
 
 namespace fd {
 
@@ -27,16 +22,7 @@ constexpr uint64_t kFnvPrime = 0x100000001b3ull;
 
 FD_HD uint64_t fnv_step(uint64_t h, unsigned char c) { return (h ^ c) * kFnvPrime; }
 
-FD_HD uint64_t fmix64_hd(uint64_t k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdULL;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ULL;
-  k ^= k >> 33;
-  return k;
-}
-
-FD_HD uint64_t hash_finish(uint64_t fnv) { return fmix64_hd(fnv); }
+FD_HD uint64_t hash_finish(uint64_t fnv) { return fmix64(fnv); }
 
 FD_HD uint64_t hash_bytes(const unsigned char* s, int64_t n) {
   uint64_t h = kFnvBasis;

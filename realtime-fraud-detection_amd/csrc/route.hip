@@ -27,22 +27,6 @@ static_assert(sizeof(ResultRecord) == FD_RESULT_RECORD_BYTES, "result record siz
 
 constexpr int kRouteBlock = 256;  // txns per block (4 waves)
 
-__device__ __forceinline__ unsigned long long rmix64(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdULL;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ULL;
-  k ^= k >> 33;
-  return k;
-}
-
-// owner GPU of a card: high 32 bits of the mix (the card table's home slot uses the low bits, so the
-// owned keys still spread over every slot of the owner's table), multiply-shift range reduction.
-__device__ __forceinline__ unsigned shard_of_dev(unsigned long long key, unsigned G) {
-  if (key == 0ull) key = 1ull;  // the card table's key normalisation (features.hip find_or_insert)
-  return (unsigned)(((rmix64(key) >> 32) * (unsigned long long)G) >> 32);
-}
-
 __device__ __forceinline__ unsigned long long lanemask_lt() {
   const unsigned lane = __lane_id();
   return lane == 0 ? 0ull : (~0ull >> (64 - lane));
@@ -58,7 +42,7 @@ __global__ void __launch_bounds__(kRouteBlock) route_count_kernel(const unsigned
   const int64_t i = (int64_t)blockIdx.x * kRouteBlock + threadIdx.x;
   if (threadIdx.x < G) cnt[threadIdx.x] = 0;
   __syncthreads();
-  const unsigned s = i < n ? shard_of_dev(key[i], G) : 0xffffffffu;
+  const unsigned s = i < n ? shard_of(key[i], G) : 0xffffffffu;
   for (unsigned t = 0; t < G; ++t) {
     const unsigned long long m = __ballot(s == t);
     if (__lane_id() == 0 && m) atomicAdd(&cnt[t], __popcll(m));
@@ -121,7 +105,7 @@ __global__ void __launch_bounds__(kRouteBlock) route_scatter_kernel(
   __shared__ int wcnt[kRouteBlock / 64][64];
   const int64_t i = (int64_t)blockIdx.x * kRouteBlock + threadIdx.x;
   const int w = threadIdx.x >> 6;
-  const unsigned s = i < n ? shard_of_dev(key[i], G) : 0xffffffffu;
+  const unsigned s = i < n ? shard_of(key[i], G) : 0xffffffffu;
   int rank = 0;
   for (unsigned t = 0; t < G; ++t) {
     const unsigned long long m = __ballot(s == t);
@@ -209,15 +193,7 @@ unsigned grid256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
-unsigned shard_of_host(unsigned long long key, unsigned G) {
-  if (key == 0ull) key = 1ull;
-  key ^= key >> 33;
-  key *= 0xff51afd7ed558ccdULL;
-  key ^= key >> 33;
-  key *= 0xc4ceb9fe1a85ec53ULL;
-  key ^= key >> 33;
-  return (unsigned)(((key >> 32) * (unsigned long long)G) >> 32);
-}
+unsigned shard_of_host(unsigned long long key, unsigned G) { return shard_of(key, G); }
 
 void launch_route_partition(Engine& e, const fd_txn_batch& t, const fd_window_inputs* extra, int64_t n, int G,
                             void* d_records, int64_t* d_counts, hipStream_t stream, DeviceBuffer* scratch,

@@ -37,15 +37,6 @@ struct __attribute__((aligned(16))) UserEntry {  // 16 B
 
 constexpr long long kHourMs = 3600000ll, kDayMs = 86400000ll;
 
-__device__ __forceinline__ unsigned long long smix(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdULL;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ULL;
-  k ^= k >> 33;
-  return k;
-}
-
 // kind (2 bits) | merchant + 1 (30 bits) | bucket (32 bits); never 0
 __device__ __host__ __forceinline__ unsigned long long agg_key(int kind, long long merchant, long long bucket) {
   return ((unsigned long long)kind << 62) | ((unsigned long long)(merchant + 1) & 0x3FFFFFFFull) << 32 |
@@ -53,7 +44,7 @@ __device__ __host__ __forceinline__ unsigned long long agg_key(int kind, long lo
 }
 
 __device__ long long agg_slot(AggEntry* T, unsigned long long mask, unsigned long long key, bool insert) {
-  unsigned long long h = smix(key) & mask;
+  unsigned long long h = fmix64(key) & mask;
   for (unsigned long long p = 0; p <= mask; ++p) {
     const unsigned long long k = __hip_atomic_load(&T[h].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (k == key) return (long long)h;
@@ -69,7 +60,7 @@ __device__ long long agg_slot(AggEntry* T, unsigned long long mask, unsigned lon
 
 // true when (tag) was newly inserted
 __device__ int user_insert(UserEntry* U, unsigned long long mask, unsigned long long tag, long long hour) {
-  unsigned long long h = smix(tag ^ 0x5851F42D4C957F2Dull) & mask;
+  unsigned long long h = fmix64(tag ^ 0x5851F42D4C957F2Dull) & mask;
   for (unsigned long long p = 0; p <= mask; ++p) {
     const unsigned long long k = __hip_atomic_load(&U[h].tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (k == tag) return 0;
@@ -124,7 +115,7 @@ __global__ void __launch_bounds__(256) sink_update_kernel(AggEntry* T, unsigned 
       // the hour's low 32 bits, as in agg_key: a negative hour (an event before 1970) sign-extended over the
       // merchant's bits would give one member to every merchant of that hour
       const unsigned long long tag =
-          smix(smix(kk) ^ ((unsigned long long)(m + 1) << 32 | ((unsigned long long)hour & 0xFFFFFFFFull))) | 1ull;
+          fmix64(fmix64(kk) ^ ((unsigned long long)(m + 1) << 32 | ((unsigned long long)hour & 0xFFFFFFFFull))) | 1ull;
       const int r = user_insert(U, umask, tag, hour);
       if (r < 0) {
         atomicOr(err, 2u);

@@ -11,7 +11,7 @@
 // followed by the replicated tables (merchants, extended merchants, vocabulary) and the Flink window event
 // logs (40-B events, card slots stripped). Restore re-inserts every record by key, so an image restores into
 // a table of any capacity and — given (shard, n_shards) — onto a different number of GPUs: each new owner
-// reads every old image and keeps the cards it owns (shard_of, route.hip), the counterpart of Flink's
+// reads every old image and keeps the cards it owns (shard_of, key_hash.h), the counterpart of Flink's
 // key-group redistribution on rescale. Sections carry FNV-1a-64 checksums (over 8-byte words).
 //
 // Snapshot per chunk of 2^18 slots: flag occupied slots -> rocPRIM select (stable: records leave in slot
@@ -99,20 +99,8 @@ __device__ __forceinline__ uint4* plane_word(const Planes& P, const RecMap& m, l
   return P.uext + slot * kUextWords + (w - m.w_uext);
 }
 
-__device__ __forceinline__ unsigned long long smix64(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdULL;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ULL;
-  k ^= k >> 33;
-  return k;
-}
-
-// route.hip shard_of_dev (keys are stored normalised: 0 -> 1)
 __device__ __forceinline__ bool owned(unsigned long long key, unsigned shard, unsigned G) {
-  if (G <= 1) return true;
-  if (key == 0ull) key = 1ull;
-  return (unsigned)(((smix64(key) >> 32) * (unsigned long long)G) >> 32) == shard;
+  return G <= 1 || shard_of(key, G) == shard;
 }
 
 // features.hip find_or_insert over a strided key array
