@@ -505,6 +505,94 @@ int fd_score_matrix_host(fd_engine* eng, const fd_blend_params* params, const in
                          int32_t ld, double* model_probs, double* fraud_prob, double* confidence,
                          uint8_t* decision, uint8_t* risk);
 
+/* ---------------------------------------------------------------- A/B tests (assign, route, record) */
+/* Replaces ABTestManager (ml/testing/ab_testing.py): a user is assigned to control (0) or treatment (1), a batch is
+   scored with the model set of each row's variant, and one result per transaction is reduced per variant on the
+   device. An engine holds FD_AB_MAX_TESTS tests, ids 0..7.
+   Assignment: bucket = fmix64((key ? key : 1) ^ salt) % 100 with murmur3's fmix64, salt = fd_hash64(test name);
+   treatment when (double)bucket < threshold, threshold being the f64 product traffic_split * 100 formed by the
+   caller (0.07 * 100 is 7.000000000000001: 8 buckets, as in the reference's comparison :126). The reference's own
+   hash() of a str is salted per process, so its assignments cannot be, and are not, reproduced; what holds is its
+   contract: one variant per (test, user), and the treatment share of the 100 buckets.
+   Recording: a row is variant (0 / nonzero), prediction, decision (enum fd_decision; another code is in no class),
+   processing_time_ms and a label (0, 1, FD_AB_NO_LABEL = the reference's None). DECLINE and REVIEW are "flagged",
+   APPROVE and APPROVE_WITH_MONITORING "passed" (:254, :278-285). Per variant: integer counts, and for the two float
+   columns their sum and M2 = sum (x - mean)^2, each as a pair hi + lo (csrc/abtest_row.h). The list the reference's
+   `precision` metric takes its moments from (:382-388) is 1.0 / 0.0 per flagged row of a variant whose rows are all
+   labeled: tp + fp values, tp of them 1.0. The counts are exact; the moments depend on how a stream is cut into
+   calls only in their last bits, and the same calls on the same state give the same bits every time (no float
+   atomics). Not part of fd_state_snapshot; one state per engine, fd_ab_state_merge_host joins the ranks' states. */
+#define FD_AB_MAX_TESTS 8
+#define FD_AB_NO_LABEL 255
+typedef struct {
+  uint64_t salt;
+  double threshold; /* traffic_split * 100, in [0, 100] */
+} fd_ab_params;
+typedef struct {
+  double sum_hi, sum_lo; /* sum x = sum_hi + sum_lo */
+  double m2_hi, m2_lo;   /* sum (x - mean)^2 = m2_hi + m2_lo */
+} fd_ab_moments;
+typedef struct {
+  int64_t rows;
+  int64_t decisions[4]; /* by enum fd_decision */
+  int64_t labeled, tp, fp, tn, fn;
+  fd_ab_moments prediction, time_ms; /* over all `rows` */
+} fd_ab_variant_state;
+typedef struct {
+  fd_ab_variant_state variant[2]; /* control, treatment */
+} fd_ab_state;
+/* One variant's arguments of fd_score_matrix_* */
+typedef struct {
+  const fd_blend_params* params;
+  const int32_t* slots;
+  const double* const* ext_probs; /* n-long columns in arrival order (host for _host, device for _device) */
+  const uint8_t* present;
+} fd_ab_model_set;
+/* create: an empty test (FD_ERR_INVALID_ARG for an id in use or a threshold outside [0, 100]); destroy frees the id;
+   clear empties its state. FD_ERR_NOT_LOADED for an id that was not created (as in every call below). */
+int fd_ab_create(fd_engine* eng, int32_t test_id, const fd_ab_params* params);
+int fd_ab_destroy(fd_engine* eng, int32_t test_id);
+int fd_ab_clear(fd_engine* eng, int32_t test_id);
+/* n keys -> n variant bytes. _device: device pointers, enqueued on the engine stream, nothing read back. */
+int fd_ab_assign_device(fd_engine* eng, int32_t test_id, const uint64_t* d_keys, int64_t n, uint8_t* d_variant);
+int fd_ab_assign_host(fd_engine* eng, int32_t test_id, const uint64_t* keys, int64_t n, uint8_t* variant);
+/* Stable partition of the row indices 0..n-1 by a variant column: idx holds the control rows in arrival order, then
+   the treatment rows in arrival order; counts = {control, treatment}. n < 2^31. */
+int fd_ab_partition_device(fd_engine* eng, const uint8_t* d_variant, int64_t n, int32_t* d_idx, int64_t* d_counts);
+int fd_ab_partition_host(fd_engine* eng, const uint8_t* variant, int64_t n, int32_t* idx, int64_t* counts);
+/* fd_score_matrix_* with one model set per variant: rows are assigned by key, gathered into partition order, each
+   variant's rows scored by fd_score_matrix's own path for that many rows and those models, and the results put back
+   in arrival order. A variant without rows launches nothing. variant (optional) receives the assignment.
+   model_probs (optional) is max(n_models) x n column-major: model m of a row's own set at m*n + row, NaN where that
+   set has fewer models. Waits once for the engine stream (the two counts size the launches). */
+int fd_ab_score_matrix_device(fd_engine* eng, int32_t test_id, const fd_ab_model_set* control,
+                              const fd_ab_model_set* treatment, const float* d_X, const uint64_t* d_keys, int64_t n,
+                              int32_t ld, uint8_t* d_variant, double* d_model_probs, double* d_fraud_prob,
+                              double* d_confidence, uint8_t* d_decision, uint8_t* d_risk);
+int fd_ab_score_matrix_host(fd_engine* eng, int32_t test_id, const fd_ab_model_set* control,
+                            const fd_ab_model_set* treatment, const float* X, const uint64_t* keys, int64_t n,
+                            int32_t ld, uint8_t* variant, double* model_probs, double* fraud_prob, double* confidence,
+                            uint8_t* decision, uint8_t* risk);
+/* n results into the test's state. processing_time_ms: an n-long column, or NULL and time_scalar applies to every
+   row (a batch caller has one time per batch). actual_fraud NULL: no row is labeled. Neither form waits for the
+   kernel. _host: columns in pageable memory have been read when the call returns; columns in pinned (page-locked)
+   memory are read asynchronously and must not change or be freed before fd_engine_sync or fd_ab_state_host. */
+int fd_ab_record_device(fd_engine* eng, int32_t test_id, const uint8_t* d_variant, const double* d_prediction,
+                        const uint8_t* d_decision, const double* d_processing_time_ms, double time_scalar,
+                        const uint8_t* d_actual_fraud, int64_t n);
+int fd_ab_record_host(fd_engine* eng, int32_t test_id, const uint8_t* variant, const double* prediction,
+                      const uint8_t* decision, const double* processing_time_ms, double time_scalar,
+                      const uint8_t* actual_fraud, int64_t n);
+/* the test's state (waits for the engine stream) */
+int fd_ab_state_host(fd_engine* eng, int32_t test_id, fd_ab_state* out);
+/* No device, no engine. merge: out = a then b (out may be a or b). bucket: the 0..99 bucket of each key.
+   record_ref: the rows in order into *state (zero it first for a new one), by the functions the kernel's lanes use. */
+int fd_ab_state_merge_host(const fd_ab_state* a, const fd_ab_state* b, fd_ab_state* out);
+int fd_ab_bucket_host(const uint64_t* keys, int64_t n, uint64_t salt, uint8_t* bucket_out);
+int fd_ab_record_ref_host(const uint8_t* variant, const double* prediction, const uint8_t* decision,
+                          const double* processing_time_ms, double time_scalar, const uint8_t* actual_fraud, int64_t n,
+                          fd_ab_state* state);
+
 /* The whole hot path for one micro-batch of transactions: fd_features_* (card state read/update,
    scoring vectors) then fd_score_matrix_* on those vectors (ld = FD_VECTOR_WIDTH). d_vectors may be
    NULL (engine scratch). Equivalent to the reference's per-transaction chain
@@ -812,7 +900,10 @@ enum fd_timing_kind { FD_TIMING_ALL = -1, FD_TIMING_XGB = 0, FD_TIMING_IFOREST =
                       FD_TIMING_ENSEMBLE = 8 /* fused XGBoost + IsolationForest + blend kernel */,
                       FD_TIMING_MLP = 9 /* the MLP head's kernel (fd_mlp_predict_*, FD_SLOT_MLP) */,
                       FD_TIMING_GRAPH = 10 /* one fd_graph_step_*: every kernel of its chunks */,
-                      FD_TIMING_TEXT = 11 /* one fd_text_features_*: every kernel of its chunks */ };
+                      FD_TIMING_TEXT = 11 /* one fd_text_features_*: every kernel of its chunks */,
+                      FD_TIMING_ABTEST = 12 /* the A/B kernels, one entry per step: assign, partition, gather,
+                                               scatter, record (the scoring passes of fd_ab_score_matrix_* count
+                                               under their own kinds) */ };
 int fd_engine_set_timing(fd_engine* eng, int enable);
 /* Engine tuning knobs (for A/B measurement; defaults are the tuned choices):
      "forest_kernel": 0 auto, 1 force the 256-thread kernel, 2 force the 1024-thread tree-split kernel

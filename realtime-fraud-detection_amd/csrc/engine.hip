@@ -2,12 +2,14 @@
 // Every entry point catches everything: status codes + a thread-local message cross the ABI,
 // exceptions never do (mirrors the reference's log-and-raise contract, ml/models/model_manager.py:302-307,
 // with the raise done by the Python shim).
+#include <algorithm>
 #include <chrono>
 #include <mutex>
 #include <cstring>
 #include <string>
 
 #include "blend_row.h"
+#include "abtest_row.h"
 #include "fd_internal.h"
 #include "graph_row.h"
 #include "host_stage.h"
@@ -270,6 +272,98 @@ static bool score_matrix(Engine& e, const fd_blend_params& p, const int32_t* slo
   return false;
 }
 
+// fd_ab_score_matrix_*: score_matrix with one model set per variant (device pointers, on e.stream). The batch is
+// assigned and partitioned, the two counts are read back (they size the launches: the one wait), then rows and
+// external columns are gathered into partition order, each variant with rows is scored by score_matrix as a batch of
+// its own, and the results are scattered back to arrival order.
+static void ab_score_matrix(Engine& e, int id, const fd_ab_model_set& c, const fd_ab_model_set& t, const float* dX,
+                            const uint64_t* d_keys, int64_t n, int32_t ld, uint8_t* d_variant, double* dMP,
+                            double* dfp, double* dconf, uint8_t* ddec, uint8_t* drisk) {
+  fd::ab_test(e, id);
+  const fd_ab_model_set* set[2] = {&c, &t};
+  for (const fd_ab_model_set* s : set) {
+    FD_REQUIRE(s->params && s->slots, FD_ERR_INVALID_ARG, "null blend params / slots");
+    FD_REQUIRE(s->params->n_models > 0 && s->params->n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG,
+               "n_models out of range");
+  }
+  FD_REQUIRE(n >= 0 && n < (1ll << 31) && ld > 0, FD_ERR_INVALID_ARG, "bad batch size / row stride");
+  if (n == 0) return;
+  FD_REQUIRE(dX && d_keys && dfp, FD_ERR_INVALID_ARG, "null X / keys / fraud_prob");
+  auto external = [](const fd_ab_model_set& s, int m) {
+    return s.slots[m] < 0 && !(s.present && !s.present[m]);
+  };
+  auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t nn = (size_t)n;
+  // before the counts are known: the index, the two counts, and the variant column when the caller wants none
+  const size_t o_cnt = pad(nn * sizeof(int32_t)), o_var = o_cnt + 256;
+  e.ab.index.ensure(o_var + (d_variant ? 0 : pad(nn)));
+  char* b0 = e.ab.index.as<char>();
+  int32_t* idx = reinterpret_cast<int32_t*>(b0);
+  int64_t* d_counts = reinterpret_cast<int64_t*>(b0 + o_cnt);
+  if (!d_variant) d_variant = reinterpret_cast<uint8_t*>(b0 + o_var);
+  fd::ab_assign(e, id, d_keys, n, d_variant);
+  fd::ab_partition(e, d_variant, n, idx, d_counts);
+  fd::AbScatter sc{};
+  FD_HIP(hipMemcpyAsync(sc.count, d_counts, sizeof(sc.count), hipMemcpyDeviceToHost, e.stream));
+  FD_HIP(hipStreamSynchronize(e.stream));
+  FD_REQUIRE(sc.count[0] >= 0 && sc.count[1] >= 0 && sc.count[0] + sc.count[1] == n, FD_ERR_HIP,
+             "internal: A/B partition counts do not add up");
+  // the batch in partition order, in its own buffer (the index above stays where it is)
+  size_t total = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = total;
+    total += pad(bytes);
+    return at;
+  };
+  const size_t o_x = take(nn * ld * sizeof(float)), o_fp = take(nn * 8), o_conf = take(nn * 8), o_dec = take(nn),
+               o_risk = take(nn);
+  size_t o_mp[2] = {}, o_ext[2][FD_MAX_MODELS] = {};
+  for (int v = 0; v < 2; ++v) {
+    sc.models[v] = set[v]->params->n_models;
+    if (dMP) o_mp[v] = take((size_t)sc.models[v] * sc.count[v] * 8);
+    for (int m = 0; m < sc.models[v]; ++m)
+      if (sc.count[v] && external(*set[v], m)) {
+        FD_REQUIRE(set[v]->ext_probs && set[v]->ext_probs[m], FD_ERR_INVALID_ARG,
+                   "model without slot needs an external probability column");
+        o_ext[v][m] = take((size_t)sc.count[v] * 8);
+      }
+  }
+  e.ab.rows.ensure(total);
+  char* b = e.ab.rows.as<char>();
+  float* Xp = reinterpret_cast<float*>(b + o_x);
+  double *p_fp = reinterpret_cast<double*>(b + o_fp), *p_conf = reinterpret_cast<double*>(b + o_conf);
+  uint8_t *p_dec = reinterpret_cast<uint8_t*>(b + o_dec), *p_risk = reinterpret_cast<uint8_t*>(b + o_risk);
+  fd::ab_gather_rows(e, dX, idx, n, ld, Xp);
+  for (int v = 0; v < 2; ++v) {
+    const int64_t first = v ? sc.count[0] : 0, cnt = sc.count[v];
+    if (cnt == 0) continue;
+    const double* ext[FD_MAX_MODELS] = {};
+    for (int m = 0; m < sc.models[v]; ++m)
+      if (external(*set[v], m)) {
+        double* col = reinterpret_cast<double*>(b + o_ext[v][m]);
+        fd::ab_gather_column(e, set[v]->ext_probs[m], idx + first, cnt, col);
+        ext[m] = col;
+      }
+    double* mp = dMP ? reinterpret_cast<double*>(b + o_mp[v]) : nullptr;
+    sc.p_mp[v] = mp;
+    score_matrix(e, *set[v]->params, set[v]->slots, ext, set[v]->present, Xp + first * ld, cnt, ld, mp, p_fp + first,
+                 dconf ? p_conf + first : nullptr, ddec ? p_dec + first : nullptr, drisk ? p_risk + first : nullptr);
+  }
+  sc.idx = idx;
+  sc.n = n;
+  sc.m_max = std::max(sc.models[0], sc.models[1]);
+  sc.p_fp = p_fp;
+  sc.p_conf = p_conf;
+  sc.p_dec = p_dec;
+  sc.p_risk = p_risk;
+  sc.fp = dfp;
+  sc.conf = dconf;
+  sc.dec = ddec;
+  sc.risk = drisk;
+  sc.mp = dMP;
+  fd::ab_scatter_results(e, sc);
+}
+
 // engine scratch for the fused path's LSTM input sequences, when a present model is the LSTM head
 static float* lstm_seq_buffer(Engine& e, const fd_blend_params& p, const int32_t* slots, const uint8_t* present,
                               int64_t n) {
@@ -349,6 +443,7 @@ int fd_engine_destroy(fd_engine* eng) {
   fd::sink_release(e);
   fd::graph_release(e);
   fd::text_release(e);
+  fd::ab_release(e);
   for (auto* b : {&e.route_blk, &e.route_blk_stream, &e.route_out, &e.route_err, &e.seq_buf, &e.seq_desc, &e.lstm.wpk, &e.lstm.wpk4, &e.lstm.bias,
                   &e.lstm.wout, &e.lstm.bout, &e.state.seq, &e.mlp.blob})
     b->release();
@@ -1984,6 +2079,214 @@ int fd_text_features_ref_host(const uint8_t* bytes, const int64_t* off, int64_t 
   FD_REQUIRE(fd::text_offsets_valid(off, n), FD_ERR_INVALID_ARG, "text offsets must start at 0 and never decrease");
   FD_REQUIRE(off[4 * n] == 0 || bytes, FD_ERR_INVALID_ARG, "null text bytes");
   fd::text_features_rows_host(bytes, off, n, feat, patterns, status);
+  FD_API_END
+}
+
+int fd_ab_create(fd_engine* eng, int32_t test_id, const fd_ab_params* params) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "null A/B params");
+  fd::ab_create(e, test_id, *params);
+  FD_API_END
+}
+
+int fd_ab_destroy(fd_engine* eng, int32_t test_id) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  fd::ab_destroy(E(eng), test_id);
+  FD_API_END
+}
+
+int fd_ab_clear(fd_engine* eng, int32_t test_id) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  fd::ab_clear(E(eng), test_id);
+  FD_API_END
+}
+
+int fd_ab_assign_device(fd_engine* eng, int32_t test_id, const uint64_t* d_keys, int64_t n, uint8_t* d_variant) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  fd::ab_assign(E(eng), test_id, d_keys, n, d_variant);
+  FD_API_END
+}
+
+int fd_ab_assign_host(fd_engine* eng, int32_t test_id, const uint64_t* keys, int64_t n, uint8_t* variant) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  fd::ab_test(e, test_id);
+  FD_REQUIRE(n >= 0 && n < (1ll << 31), FD_ERR_INVALID_ARG, "batch size out of range");
+  if (n == 0) return FD_OK;
+  FD_REQUIRE(keys && variant, FD_ERR_INVALID_ARG, "null keys / variant");
+  Stage st(e);
+  const uint64_t* dk;
+  uint8_t* dv;
+  st.in(dk, keys, (size_t)n);
+  st.out(dv, variant, (size_t)n);
+  st.upload();
+  fd::ab_assign(e, test_id, dk, n, dv);
+  st.download();
+  FD_API_END
+}
+
+int fd_ab_partition_device(fd_engine* eng, const uint8_t* d_variant, int64_t n, int32_t* d_idx, int64_t* d_counts) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  fd::ab_partition(E(eng), d_variant, n, d_idx, d_counts);
+  FD_API_END
+}
+
+int fd_ab_partition_host(fd_engine* eng, const uint8_t* variant, int64_t n, int32_t* idx, int64_t* counts) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(n >= 0 && n < (1ll << 31) && counts, FD_ERR_INVALID_ARG, "bad batch size / null counts");
+  FD_REQUIRE(n == 0 || (variant && idx), FD_ERR_INVALID_ARG, "null variant / index");
+  Stage st(e);
+  const uint8_t* dv;
+  int32_t* di;
+  int64_t* dc;
+  st.in(dv, variant, (size_t)n);
+  st.out(di, idx, (size_t)n);
+  st.out(dc, counts, 2);
+  st.upload();
+  fd::ab_partition(e, dv, n, di, dc);
+  st.download();
+  FD_API_END
+}
+
+int fd_ab_score_matrix_device(fd_engine* eng, int32_t test_id, const fd_ab_model_set* control,
+                              const fd_ab_model_set* treatment, const float* d_X, const uint64_t* d_keys, int64_t n,
+                              int32_t ld, uint8_t* d_variant, double* d_model_probs, double* d_fraud_prob,
+                              double* d_confidence, uint8_t* d_decision, uint8_t* d_risk) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(control && treatment, FD_ERR_INVALID_ARG, "null model set");
+  ab_score_matrix(e, test_id, *control, *treatment, d_X, d_keys, n, ld, d_variant, d_model_probs, d_fraud_prob,
+                  d_confidence, d_decision, d_risk);
+  FD_API_END
+}
+
+int fd_ab_score_matrix_host(fd_engine* eng, int32_t test_id, const fd_ab_model_set* control,
+                            const fd_ab_model_set* treatment, const float* X, const uint64_t* keys, int64_t n,
+                            int32_t ld, uint8_t* variant, double* model_probs, double* fraud_prob, double* confidence,
+                            uint8_t* decision, uint8_t* risk) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(control && treatment, FD_ERR_INVALID_ARG, "null model set");
+  FD_REQUIRE(n >= 0 && n < (1ll << 31) && ld > 0, FD_ERR_INVALID_ARG, "bad batch size / row stride");
+  fd::ab_test(e, test_id);
+  if (n == 0) return FD_OK;
+  FD_REQUIRE(X && keys && fraud_prob, FD_ERR_INVALID_ARG, "null X / keys / fraud_prob");
+  Stage st(e);
+  const float* dX;
+  const uint64_t* dk;
+  const double* dext[2][FD_MAX_MODELS] = {};
+  fd_ab_model_set dset[2] = {*control, *treatment};
+  int m_max = 0;
+  st.in(dX, X, (size_t)n * ld);
+  st.in(dk, keys, (size_t)n);
+  for (int v = 0; v < 2; ++v) {  // the external columns, n-long in arrival order
+    const fd_ab_model_set& s = dset[v];
+    FD_REQUIRE(s.params && s.slots, FD_ERR_INVALID_ARG, "null blend params / slots");
+    const int M = s.params->n_models;
+    FD_REQUIRE(M > 0 && M <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, "n_models out of range");
+    m_max = std::max(m_max, M);
+    for (int m = 0; m < M; ++m) {
+      if (s.slots[m] >= 0 || (s.present && !s.present[m])) continue;
+      FD_REQUIRE(s.ext_probs && s.ext_probs[m], FD_ERR_INVALID_ARG,
+                 "model without slot needs an external probability column");
+      st.in(dext[v][m], s.ext_probs[m], (size_t)n);
+    }
+    dset[v].ext_probs = dext[v];
+  }
+  uint8_t *dvar, *ddec, *drisk;
+  double *dMP, *dfp, *dconf;
+  st.out(dvar, variant, (size_t)n);
+  st.out(dMP, model_probs, (size_t)n * m_max);
+  st.out(dfp, fraud_prob, (size_t)n);
+  st.out(dconf, confidence, (size_t)n);
+  st.out(ddec, decision, (size_t)n);
+  st.out(drisk, risk, (size_t)n);
+  st.upload();
+  ab_score_matrix(e, test_id, dset[0], dset[1], dX, dk, n, ld, dvar, dMP, dfp, dconf, ddec, drisk);
+  st.download();
+  FD_API_END
+}
+
+int fd_ab_record_device(fd_engine* eng, int32_t test_id, const uint8_t* d_variant, const double* d_prediction,
+                        const uint8_t* d_decision, const double* d_processing_time_ms, double time_scalar,
+                        const uint8_t* d_actual_fraud, int64_t n) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  fd::ab_record(E(eng), test_id, d_variant, d_prediction, d_decision, d_processing_time_ms, time_scalar,
+                d_actual_fraud, n);
+  FD_API_END
+}
+
+int fd_ab_record_host(fd_engine* eng, int32_t test_id, const uint8_t* variant, const double* prediction,
+                      const uint8_t* decision, const double* processing_time_ms, double time_scalar,
+                      const uint8_t* actual_fraud, int64_t n) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  fd::ab_test(e, test_id);
+  FD_REQUIRE(n >= 0, FD_ERR_INVALID_ARG, "negative n");
+  if (n == 0) return FD_OK;
+  FD_REQUIRE(variant && prediction && decision, FD_ERR_INVALID_ARG, "null variant / prediction / decision");
+  Stage st(e);
+  const uint8_t *dv, *dd, *dl;
+  const double *dp, *dt;
+  st.in(dv, variant, (size_t)n);
+  st.in(dp, prediction, (size_t)n);
+  st.in(dd, decision, (size_t)n);
+  st.in(dt, processing_time_ms, (size_t)n);
+  st.in(dl, actual_fraud, (size_t)n);
+  st.upload();
+  // No wait, as in fd_sink_update_host: fd_ab_state_host is ordered behind the kernel on e.stream. The caller may
+  // reuse its columns at once only because a copy from pageable memory has read its source when hipMemcpyAsync
+  // returns; columns in pinned memory are read later, and must stay as they are until the stream has passed this call
+  // (include/fdengine.h says so).
+  fd::ab_record(e, test_id, dv, dp, dd, dt, time_scalar, dl, n);
+  FD_API_END
+}
+
+int fd_ab_state_host(fd_engine* eng, int32_t test_id, fd_ab_state* out) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  fd::ab_state_read(E(eng), test_id, out);
+  FD_API_END
+}
+
+int fd_ab_state_merge_host(const fd_ab_state* a, const fd_ab_state* b, fd_ab_state* out) {
+  FD_API_BEGIN
+  FD_REQUIRE(a && b && out, FD_ERR_INVALID_ARG, "null state");
+  fd_ab_state r = *a;
+  for (int v = 0; v < 2; ++v) fd::ab_merge(r.variant[v], b->variant[v]);
+  *out = r;
+  FD_API_END
+}
+
+int fd_ab_bucket_host(const uint64_t* keys, int64_t n, uint64_t salt, uint8_t* bucket_out) {
+  FD_API_BEGIN
+  FD_REQUIRE(n >= 0 && (n == 0 || (keys && bucket_out)), FD_ERR_INVALID_ARG, "bad arguments");
+  for (int64_t i = 0; i < n; ++i) bucket_out[i] = (uint8_t)fd::ab_bucket(keys[i], salt);
+  FD_API_END
+}
+
+int fd_ab_record_ref_host(const uint8_t* variant, const double* prediction, const uint8_t* decision,
+                          const double* processing_time_ms, double time_scalar, const uint8_t* actual_fraud, int64_t n,
+                          fd_ab_state* state) {
+  FD_API_BEGIN
+  FD_REQUIRE(n >= 0 && state && (n == 0 || (variant && prediction && decision)), FD_ERR_INVALID_ARG, "bad arguments");
+  for (int64_t i = 0; i < n; ++i)
+    fd::ab_add_row(state->variant[variant[i] ? 1 : 0], prediction[i], decision[i],
+                   processing_time_ms ? processing_time_ms[i] : time_scalar,
+                   actual_fraud ? actual_fraud[i] : (uint8_t)FD_AB_NO_LABEL);
   FD_API_END
 }
 

@@ -293,6 +293,35 @@ struct TextState {
   unsigned long long calls = 0;  // counter "text_calls"
 };
 
+// A/B tests (abtest.hip): the tests' parameters on the host, their accumulators on the device
+struct AbTest {
+  bool live = false;
+  uint64_t salt = 0;
+  double threshold = 0.0;
+};
+struct AbState {
+  AbTest tests[FD_AB_MAX_TESTS];
+  DeviceBuffer state;     // fd_ab_state per test id
+  DeviceBuffer partials;  // one fd_ab_state per workgroup of the record kernel, then its ticket
+  DeviceBuffer part;      // partition: control rows per workgroup, scanned in place
+  DeviceBuffer index;     // fd_ab_score_matrix_* (engine.hip): the partition's index, its two counts, the variants
+  DeviceBuffer rows;      // ... and the batch in partition order with its results
+};
+// ab_scatter_results: partition-order results (p_*) back to arrival order; a null output is skipped
+struct AbScatter {
+  const int32_t* idx;
+  int64_t n;
+  int64_t count[2];  // rows per variant
+  int models[2];     // n_models per variant
+  int m_max;
+  const double *p_fp, *p_conf;
+  const uint8_t *p_dec, *p_risk;
+  const double* p_mp[2];  // models[v] x count[v], column-major
+  double *fp, *conf;
+  uint8_t *dec, *risk;
+  double* mp;  // m_max x n
+};
+
 // MLP head (mlp.hip): the packed model (header, per layer the A operands in the chained k order, padded biases)
 struct MlpModel {
   bool loaded = false;
@@ -575,6 +604,7 @@ struct Engine {
   unsigned long long mlp_total = 0;  // counter "mlp_launches"
   GraphState graph;
   TextState text;
+  AbState ab;
   WindowState windows;
   IngestTables ingest;
   SinkState sink;
@@ -852,6 +882,20 @@ void text_release(Engine& e);
 int64_t text_nonascii_rows(Engine& e);  // waits for the engine stream
 void text_features(Engine& e, const uint8_t* d_bytes, const int64_t* d_off, int64_t n, double* d_feat,
                    uint8_t* d_patterns, uint8_t* d_status);  // device pointers, on e.stream; outputs may be null
+// abtest.hip (device pointers, on e.stream)
+const AbTest& ab_test(Engine& e, int id);  // FD_ERR_NOT_LOADED unless created
+void ab_create(Engine& e, int id, const fd_ab_params& p);
+void ab_destroy(Engine& e, int id);
+void ab_clear(Engine& e, int id);
+void ab_release(Engine& e);
+void ab_assign(Engine& e, int id, const uint64_t* d_keys, int64_t n, uint8_t* d_variant);
+void ab_partition(Engine& e, const uint8_t* d_variant, int64_t n, int32_t* d_idx, int64_t* d_counts);
+void ab_gather_rows(Engine& e, const float* d_X, const int32_t* d_idx, int64_t n, int32_t ld, float* d_Xp);
+void ab_gather_column(Engine& e, const double* d_col, const int32_t* d_idx, int64_t count, double* d_out);
+void ab_scatter_results(Engine& e, const AbScatter& a);
+void ab_record(Engine& e, int id, const uint8_t* d_variant, const double* d_prediction, const uint8_t* d_decision,
+               const double* d_time_ms, double time_scalar, const uint8_t* d_label, int64_t n);
+void ab_state_read(Engine& e, int id, fd_ab_state* out);  // waits for the engine stream
 // model_io.hip: the unchanged XGBoost 2.0.3 JSON model file, flattened (fdengine/forest.py semantics)
 struct XgbModel {
   int num_feature = 0;

@@ -155,6 +155,28 @@ class fd_text_batch(C.Structure):
     _fields_ = [("bytes", C.c_void_p), ("off", C.c_void_p)]
 
 
+class fd_ab_params(C.Structure):
+    _fields_ = [("salt", C.c_uint64), ("threshold", C.c_double)]
+
+
+class fd_ab_moments(C.Structure):
+    _fields_ = [("sum_hi", C.c_double), ("sum_lo", C.c_double), ("m2_hi", C.c_double), ("m2_lo", C.c_double)]
+
+
+class fd_ab_variant_state(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("decisions", C.c_int64 * 4), ("labeled", C.c_int64), ("tp", C.c_int64),
+                ("fp", C.c_int64), ("tn", C.c_int64), ("fn", C.c_int64), ("prediction", fd_ab_moments),
+                ("time_ms", fd_ab_moments)]
+
+
+class fd_ab_state(C.Structure):
+    _fields_ = [("variant", fd_ab_variant_state * 2)]
+
+
+class fd_ab_model_set(C.Structure):
+    _fields_ = [("params", C.c_void_p), ("slots", C.c_void_p), ("ext_probs", C.c_void_p), ("present", C.c_void_p)]
+
+
 class fd_users(C.Structure):
     _fields_ = [("n", C.c_int64), ("key", C.c_void_p), ("avg_amount", C.c_void_p),
                 ("account_age_days", C.c_void_p), ("device_fp", C.c_void_p)]
@@ -179,6 +201,7 @@ FD_TIMING_ENSEMBLE = 8
 FD_TIMING_MLP = 9
 FD_TIMING_GRAPH = 10
 FD_TIMING_TEXT = 11
+FD_TIMING_ABTEST = 12
 
 # JSON ingest codec (fd_ingest_out column order and dtypes)
 INGEST_FIELDS = (("card_key", "<u8"), ("ts_ms", "<i8"), ("amount_cents", "<i8"), ("merchant", "<i4"),
@@ -244,6 +267,8 @@ TEXT_COLUMNS = ("merchant_name_length", "description_length", "total_text_length
                 "description_word_count", "total_word_count")
 TEXT_PATTERNS = ("crypto_keywords", "gift_card_keywords", "urgent_language", "suspicious_merchant",
                  "known_scam_patterns")
+FD_AB_MAX_TESTS = 8
+FD_AB_NO_LABEL = 255
 FD_SEQ_INPUT = 16
 FD_MAX_SHARDS = 64
 FD_ROUTE_RECORD_BYTES = 48
@@ -319,6 +344,23 @@ SIGNATURES = {
     "fd_text_features_device": (C.c_int, [_vp, C.POINTER(fd_text_batch), _i64, _vp, _vp, _vp]),
     "fd_text_features_host": (C.c_int, [_vp, C.POINTER(fd_text_batch), _i64, _vp, _vp, _vp]),
     "fd_text_features_ref_host": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "fd_ab_create": (C.c_int, [_vp, _i32, C.POINTER(fd_ab_params)]),
+    "fd_ab_destroy": (C.c_int, [_vp, _i32]),
+    "fd_ab_clear": (C.c_int, [_vp, _i32]),
+    "fd_ab_assign_device": (C.c_int, [_vp, _i32, _vp, _i64, _vp]),
+    "fd_ab_assign_host": (C.c_int, [_vp, _i32, _vp, _i64, _vp]),
+    "fd_ab_partition_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "fd_ab_partition_host": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "fd_ab_score_matrix_device": (C.c_int, [_vp, _i32, C.POINTER(fd_ab_model_set), C.POINTER(fd_ab_model_set), _vp,
+                                            _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fd_ab_score_matrix_host": (C.c_int, [_vp, _i32, C.POINTER(fd_ab_model_set), C.POINTER(fd_ab_model_set), _vp,
+                                          _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fd_ab_record_device": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, C.c_double, _vp, _i64]),
+    "fd_ab_record_host": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, C.c_double, _vp, _i64]),
+    "fd_ab_state_host": (C.c_int, [_vp, _i32, C.POINTER(fd_ab_state)]),
+    "fd_ab_state_merge_host": (C.c_int, [C.POINTER(fd_ab_state), C.POINTER(fd_ab_state), C.POINTER(fd_ab_state)]),
+    "fd_ab_bucket_host": (C.c_int, [_vp, _i64, C.c_uint64, _vp]),
+    "fd_ab_record_ref_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, _vp, _i64, C.POINTER(fd_ab_state)]),
     "fd_features_seq_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _vp, _vp, _vp]),
     "fd_shard_of_host": (C.c_int, [_vp, _i64, _i32, _vp]),
     "fd_route_partition_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _i32, _vp, _vp]),

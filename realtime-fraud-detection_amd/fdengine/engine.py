@@ -522,6 +522,131 @@ class FraudEngine:
         N.call("fd_text_features_device", self._h, C.byref(b), int(n), *(C.c_void_p(p) if p else None
                                                                         for p in (feat_ptr, patterns_ptr, status_ptr)))
 
+    # ------------------------------------------------------------------ A/B tests (fdengine/ab_testing.py)
+    def ab_create(self, test_id: int, salt: int, threshold: float) -> None:
+        """An empty test under id 0..FD_AB_MAX_TESTS-1. salt: fd_hash64 of the test's name; threshold: the f64
+        traffic_split * 100 (formed by the caller: buckets below it are treatment)."""
+        p = N.fd_ab_params(int(salt), float(threshold))
+        N.call("fd_ab_create", self._h, int(test_id), C.byref(p))
+
+    def ab_destroy(self, test_id: int) -> None:
+        N.call("fd_ab_destroy", self._h, int(test_id))
+
+    def ab_clear(self, test_id: int) -> None:
+        N.call("fd_ab_clear", self._h, int(test_id))
+
+    def ab_assign(self, test_id: int, keys) -> np.ndarray:
+        """uint64 user keys -> uint8 [n]: 0 control, 1 treatment."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        out = np.empty(len(keys), np.uint8)
+        N.call("fd_ab_assign_host", self._h, int(test_id), _ptr(keys), len(keys), _ptr(out))
+        return out
+
+    def ab_assign_device(self, test_id: int, keys_ptr: int, n: int, variant_ptr: int) -> None:
+        N.call("fd_ab_assign_device", self._h, int(test_id), C.c_void_p(keys_ptr), int(n), C.c_void_p(variant_ptr))
+
+    def ab_partition(self, variant):
+        """uint8 [n] variants -> (int32 [n] row indices: control rows in arrival order, then treatment rows in arrival
+        order; int64 [2] rows per variant)."""
+        variant = np.ascontiguousarray(variant, np.uint8)
+        idx = np.empty(len(variant), np.int32)
+        counts = np.empty(2, np.int64)
+        N.call("fd_ab_partition_host", self._h, _ptr(variant), len(variant), _ptr(idx), _ptr(counts))
+        return idx, counts
+
+    def ab_partition_device(self, variant_ptr: int, n: int, idx_ptr: int, counts_ptr: int) -> None:
+        N.call("fd_ab_partition_device", self._h, C.c_void_p(variant_ptr), int(n), C.c_void_p(idx_ptr),
+               C.c_void_p(counts_ptr))
+
+    @staticmethod
+    def _ab_model_set(ms: dict, device: bool):
+        """{"params", "slots", "ext_probs"?, "present"?} (score_matrix's arguments) -> (fd_ab_model_set, what it
+        points into). ext_probs: arrays, or device pointers when `device`."""
+        params = ms["params"]
+        M = params.n_models
+        slots = list(ms["slots"])
+        sl = np.array(slots + [-1] * (N.FD_MAX_MODELS - len(slots)), np.int32)
+        present = ms.get("present")
+        pres = np.array([1] * M if present is None else list(present), np.uint8)
+        ext = (C.c_void_p * N.FD_MAX_MODELS)()
+        keep = [params, sl, pres, ext]
+        cols = ms.get("ext_probs")
+        for m in range(M):
+            if sl[m] < 0 and pres[m]:
+                if device:
+                    ext[m] = int(cols[m])
+                else:
+                    col = np.ascontiguousarray(cols[m], dtype=np.float64)
+                    keep.append(col)
+                    ext[m] = col.ctypes.data
+        s = N.fd_ab_model_set(C.addressof(params), sl.ctypes.data, C.addressof(ext), pres.ctypes.data)
+        return s, keep
+
+    def ab_score_matrix(self, test_id: int, control: dict, treatment: dict, X: np.ndarray, keys):
+        """score_matrix with one model set per variant (each a dict of score_matrix's arguments: params, slots,
+        ext_probs, present; ext_probs columns are n long, in X's row order). Row i is scored by the set of its user
+        key's variant. -> (variant u8 [n], model_probs [max M, n] f64 with NaN where the row's set has fewer models,
+        fraud_prob, confidence, decision u8, risk u8)."""
+        X = np.ascontiguousarray(np.asarray(X, dtype=np.float32))
+        n, ld = X.shape
+        keys = np.ascontiguousarray(keys, np.uint64)
+        if len(keys) != n:
+            raise ValueError("one key per row")
+        cs, keep_c = self._ab_model_set(control, False)
+        ts, keep_t = self._ab_model_set(treatment, False)
+        m_max = max(control["params"].n_models, treatment["params"].n_models)
+        var = np.empty(n, np.uint8)
+        mp = np.empty((m_max, n), np.float64)
+        fp = np.empty(n, np.float64)
+        conf = np.empty(n, np.float64)
+        dec = np.empty(n, np.uint8)
+        risk = np.empty(n, np.uint8)
+        N.call("fd_ab_score_matrix_host", self._h, int(test_id), C.byref(cs), C.byref(ts), _ptr(X), _ptr(keys), n, ld,
+               _ptr(var), _ptr(mp), _ptr(fp), _ptr(conf), _ptr(dec), _ptr(risk))
+        del keep_c, keep_t
+        return var, mp, fp, conf, dec, risk
+
+    def ab_score_matrix_device(self, test_id: int, control: dict, treatment: dict, X_ptr: int, keys_ptr: int, n: int,
+                               ld: int, fp_ptr: int, variant_ptr: int = 0, mp_ptr: int = 0, conf_ptr: int = 0,
+                               dec_ptr: int = 0, risk_ptr: int = 0) -> None:
+        """Device pointers (ext_probs entries too); waits once for the engine stream, reads two counts back."""
+        cs, keep_c = self._ab_model_set(control, True)
+        ts, keep_t = self._ab_model_set(treatment, True)
+        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        N.call("fd_ab_score_matrix_device", self._h, int(test_id), C.byref(cs), C.byref(ts), C.c_void_p(X_ptr),
+               C.c_void_p(keys_ptr), int(n), int(ld), opt(variant_ptr), opt(mp_ptr), C.c_void_p(fp_ptr), opt(conf_ptr),
+               opt(dec_ptr), opt(risk_ptr))
+        del keep_c, keep_t
+
+    def ab_record(self, test_id: int, variant, prediction, decision, processing_time_ms, actual_fraud=None) -> None:
+        """n results into the test's device state. processing_time_ms: an array, or one float for every row.
+        actual_fraud: None (no labels) or uint8 [n] of 0, 1, FD_AB_NO_LABEL."""
+        variant = np.ascontiguousarray(variant, np.uint8)
+        n = len(variant)
+        prediction = np.ascontiguousarray(prediction, np.float64)
+        decision = np.ascontiguousarray(decision, np.uint8)
+        scalar = np.ndim(processing_time_ms) == 0
+        times = None if scalar else np.ascontiguousarray(processing_time_ms, np.float64)
+        label = None if actual_fraud is None else np.ascontiguousarray(actual_fraud, np.uint8)
+        for a in (prediction, decision, times, label):
+            if a is not None and len(a) != n:
+                raise ValueError("columns of different lengths")
+        N.call("fd_ab_record_host", self._h, int(test_id), _ptr(variant), _ptr(prediction), _ptr(decision), _ptr(times),
+               float(processing_time_ms) if scalar else 0.0, _ptr(label), n)
+
+    def ab_record_device(self, test_id: int, variant_ptr: int, prediction_ptr: int, decision_ptr: int, n: int,
+                         time_ptr: int = 0, time_scalar: float = 0.0, label_ptr: int = 0) -> None:
+        """Device pointers, on the engine stream, nothing read back. time_ptr 0: time_scalar for every row."""
+        N.call("fd_ab_record_device", self._h, int(test_id), C.c_void_p(variant_ptr), C.c_void_p(prediction_ptr),
+               C.c_void_p(decision_ptr), C.c_void_p(time_ptr) if time_ptr else None, float(time_scalar),
+               C.c_void_p(label_ptr) if label_ptr else None, int(n))
+
+    def ab_state(self, test_id: int) -> N.fd_ab_state:
+        """The test's two accumulators (waits for the engine stream)."""
+        out = N.fd_ab_state()
+        N.call("fd_ab_state_host", self._h, int(test_id), C.byref(out))
+        return out
+
     # ------------------------------------------------------------------ card-hash sharding (fdengine/sharding.py)
     def route_partition_device(self, txn_ptrs: dict, n: int, n_shards: int, records_ptr: int, counts_ptr: int) -> None:
         """Group one device-resident micro-batch by owner GPU: n records of FD_ROUTE_RECORD_BYTES at
