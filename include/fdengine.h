@@ -178,6 +178,18 @@ int fd_pack_forest_binned_host(const fd_forest_params* params, const fd_tree_arr
                                int64_t blob_cap, float* thresholds, int64_t thr_cap, int32_t* offsets,
                                fd_pack_info* info);
 
+/* Host-only: the forest contracted against the constant slots of the compact scoring vector. The pipelined stream's
+   compact and split rows carry 22 varying slots; of the other 42, slots 12, 24, 25, 33 and 34 are always 0.5 and the
+   rest 0 (the reference's feature map at serving time). Every split on such a slot is replaced by the child that value
+   takes (left iff value < threshold in f32, the packers' comparison; never NaN, so default_left plays no part), which
+   is what the fused kernel walks on those rows (engine option ensemble_contract). Surviving nodes keep their order
+   (a tree with no such split comes back unchanged); a tree that resolves to one leaf becomes a root over two leaves
+   of that value. XGBoost and IsolationForest kinds.
+   Call with out == NULL for *n_nodes, then with out's arrays sized n_trees + 1 (offsets) and *n_nodes (the rest).
+   depths (optional, n_trees): each contracted tree's depth, at least 1; n_pruned (optional): splits removed. */
+int fd_contract_forest_host(const fd_forest_params* params, const fd_tree_arrays* trees, int64_t* n_nodes,
+                            fd_tree_arrays* out, int32_t* depths, int64_t* n_pruned);
+
 /* Sparse (pointer) layout, host-only repack: trees of ANY depth and any kind keep their shape (no padding). It is the
    only layout of FD_FOREST_SKLEARN_PROBA and of forests deeper than 10 levels (fd_load_forest picks it for them;
    fd_forest_info then reports the true depth), and what engine option forest_kernel = 11 walks for any forest.
@@ -918,6 +930,9 @@ int fd_engine_set_timing(fd_engine* eng, int enable);
      "ensemble_chunks": the fused kernel's chunk layout, 0 (default) auto: compact once the engine has RCCL
      communicators (fd_comm_init), else wide; 1 wide (24 XGBoost / 16 IsolationForest trees per chunk, 148 KB of
      LDS); 2 compact (20 / 12, 132 KB: room for an RCCL kernel on the same CU). Outputs are identical.
+     "ensemble_contract": the fused kernel on the pipelined stream's compact / split rows walks the forests contracted
+     against the rows' constant slots (fd_contract_forest_host): 1 (default) each tree to the deepest of its wave's
+     trees, 2 each tree to its own depth (slower: an A/B option), 0 the full forests. Outputs are identical.
      "lstm_rows": LSTM tile, 0 auto (4 transactions below 4096, else 16), 4 or 16
      "mlp_form": the MLP head's kernel for the reference shape (3 layers, padded widths 64): 0 (default) weights in
      registers, 1 the LDS form every other shape takes
@@ -964,7 +979,9 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    "pipelined_batches" (batches through fd_score_batch_pipelined /
    fd_score_records_pipelined so far), "pipelined_compact_batches" (of those, scored by the fused ensemble kernel from
    the compact 64-B rows: no vectors requested), "ensemble_single_launches" (fd_forest_predict batches scored by the
-   fused kernel over one forest), "forest_sparse_launches" (launches of the sparse-layout forest kernel),
+   fused kernel over one forest), "ensemble_contracted_launches" (fused launches over the contracted forests),
+   "ensemble_nodes_pruned" (splits the current plan's contraction removed), "ensemble_node_steps_per_txn" (tree levels
+   walked per transaction by the last fused pair launch), "forest_sparse_launches" (launches of the sparse-layout forest kernel),
    "mlp_launches" (launches of the MLP head's kernel), "graph_steps" (fd_graph_step_* calls with n > 0),
    "text_calls" (fd_text_features_device / _host calls with n > 0), "text_nonascii_rows" (rows those calls flagged
    FD_TEXT_NONASCII; reading it waits for the engine stream),

@@ -580,6 +580,15 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
   } else if (k == "ensemble_single_launches") {  // fd_forest_predict batches scored by the fused kernel over one
     // forest (probabilities, optionally raw scores; no leaf ids): config 2's timed kernel, ensemble_kernel<8,2>
     *value = (int64_t)e.ens_single_total;
+  } else if (k == "ensemble_contracted_launches") {  // fused launches over the contracted forests (compact / split rows,
+    // option ensemble_contract, a plan the contraction shortened)
+    *value = (int64_t)e.ens_contract_total;
+  } else if (k == "ensemble_nodes_pruned") {  // the current pair plan: splits on constant slots resolved at load, and
+    // the splits of the subtrees that went with them
+    *value = e.ens.valid ? (int64_t)e.ens.nodes_pruned : 0;
+  } else if (k == "ensemble_node_steps_per_txn") {  // the last fused pair launch: tree levels walked per transaction
+    // over both forests (the sum of the depths as walked; n_trees x D on the uncontracted path)
+    *value = (int64_t)e.ens_steps_last;
   } else if (k == "forest_sparse_launches") {  // launches of forest_sparse_kernel: predict_proba forests, forests
     // deeper than 10 levels, and any forest under option forest_kernel = 11
     *value = (int64_t)e.sparse_total;
@@ -656,6 +665,17 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value) {
     // communicators, else wide), 1 wide (24 / 16 trees), 2 compact (20 / 12: LDS room for an RCCL kernel beside)
     FD_REQUIRE(value >= 0 && value <= 2, FD_ERR_INVALID_ARG, "ensemble_chunks must be 0, 1 or 2");
     e.ens_chunks = (int)value;
+  } else if (k == "ensemble_contract") {  // fused kernel on compact / split rows: the forests contracted against the
+    // rows' constant slots (ensemble.hip contract_forest_host) and walked to 1 (default) the deepest of each wave's
+    // trees (a fixed-depth walk chosen per wave and chunk), 2 each tree's own depth (uniform branches inside the walk:
+    // measured slower); 0 the full forests at the common depth (outputs identical in every mode). A change
+    // rebuilds the plan's chunks: the device is idle first
+    FD_REQUIRE(value >= 0 && value <= 2, FD_ERR_INVALID_ARG, "ensemble_contract must be 0, 1 or 2");
+    if ((int)value != e.ens_contract) {
+      e.activate();
+      FD_HIP(hipDeviceSynchronize());
+    }
+    e.ens_contract = (int)value;
   } else if (k == "compact_vectors") {  // pipelined stream, the fused kernel's batches when nobody asked for the
     // vectors: 2 (default) split rows — the card-independent half finished by the slot pass, the bucket pass reads
     // 32-B prep records and writes the card half (features.hip Prep32 / RowA / RowB); 1 the compact 64-B row; 0 the
@@ -842,6 +862,32 @@ int fd_pack_forest_host(const fd_forest_params* params, const fd_tree_arrays* tr
   if (leaf_ids) {
     FD_REQUIRE(ids_cap >= (int64_t)hp.leaf_ids.size(), FD_ERR_INVALID_ARG, "leaf id buffer too small");
     std::memcpy(leaf_ids, hp.leaf_ids.data(), hp.leaf_ids.size() * sizeof(int32_t));
+  }
+  FD_API_END
+}
+
+int fd_contract_forest_host(const fd_forest_params* params, const fd_tree_arrays* trees, int64_t* n_nodes,
+                            fd_tree_arrays* out, int32_t* depths, int64_t* n_pruned) {
+  FD_API_BEGIN
+  FD_REQUIRE(params && trees, FD_ERR_INVALID_ARG, "null params/trees");
+  const fd::ContractedForest c = fd::contract_forest_host(*params, *trees);
+  const int32_t T = (int32_t)c.off.size() - 1;
+  const int64_t M = (int64_t)c.left.size();
+  if (n_nodes) *n_nodes = M;
+  if (n_pruned) *n_pruned = (int64_t)c.pruned;
+  if (depths) std::memcpy(depths, c.depth.data(), (size_t)T * 4);
+  if (out) {
+    FD_REQUIRE(out->tree_offsets && out->left && out->right && out->feature && out->threshold && out->default_left &&
+                   out->leaf_value,
+               FD_ERR_INVALID_ARG, "incomplete output arrays");
+    out->n_trees = T;
+    std::memcpy(const_cast<int64_t*>(out->tree_offsets), c.off.data(), (size_t)(T + 1) * 8);
+    std::memcpy(const_cast<int32_t*>(out->left), c.left.data(), (size_t)M * 4);
+    std::memcpy(const_cast<int32_t*>(out->right), c.right.data(), (size_t)M * 4);
+    std::memcpy(const_cast<int32_t*>(out->feature), c.feature.data(), (size_t)M * 4);
+    std::memcpy(const_cast<double*>(out->threshold), c.threshold.data(), (size_t)M * 8);
+    std::memcpy(const_cast<uint8_t*>(out->default_left), c.dleft.data(), (size_t)M);
+    std::memcpy(const_cast<double*>(out->leaf_value), c.leaf.data(), (size_t)M * 8);
   }
   FD_API_END
 }
@@ -1282,8 +1328,7 @@ static void pipe_step(Engine& e, const fd_blend_params* params, const int32_t* s
   // records; the lean bucket pass only, and not with LSTM history in the card state)
   int compact = (e.compact_vectors && d_vectors == nullptr && fd::ensemble_applies(e, *params, slots, present, n))
                     ? e.compact_vectors : 0;
-  e.pipe_vec[s].ensure((size_t)n * FD_VECTOR_WIDTH * 4);
-  float* vec = e.pipe_vec[s].as<float>();
+  float* vec = nullptr;
   const int sr = (int)(e.pipe_iter % (unsigned long long)Engine::kSplitRing);  // split rows: this batch's ring buffer
   float* seq = nullptr;
   bool want_seq = false;
@@ -1305,6 +1350,9 @@ static void pipe_step(Engine& e, const fd_blend_params* params, const int32_t* s
     e.pipe_split[sr].ensure((size_t)n * 64);
     vec = e.pipe_split[sr].as<float>();
     if (Ss && e.pipe_done_live[sr]) FD_HIP(hipStreamWaitEvent(Ss, e.pipe_done_ev[sr], 0));  // batch i - 4's
+  } else {  // the 64-wide vectors or compact rows: the slot's own buffer (split-row batches never touch it)
+    e.pipe_vec[s].ensure((size_t)n * FD_VECTOR_WIDTH * 4);
+    vec = e.pipe_vec[s].as<float>();
   }
   {
     struct SlotPass {  // launch_grouped reads these for this call only

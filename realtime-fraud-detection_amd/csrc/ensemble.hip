@@ -23,6 +23,10 @@
 // (IsolationForest): both the reference's sequential sums, bit for bit. Epilogue (tree group 0, one thread
 // per transaction): sigmoid / IsolationForest transform, blend_row, outputs (columns, or the 24-B route
 // result records of the owner GPU).
+//
+// Compact / split rows (the pipelined stream) hold 42 constant slots: the plan also packs the forests with every
+// split on such a slot decided (contract_forest_host), and the VD instantiations walk each wave's trees only to the
+// deepest of them (walk_pack_var; engine option ensemble_contract). 64-wide rows keep the full forests.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -48,6 +52,98 @@ void forest_loaded(PackedForest& pf, const fd_forest_params& p, const fd_tree_ar
     pf.t_dleft.assign(t.default_left, t.default_left + m);
   else
     pf.t_dleft.assign((size_t)m, 0);
+}
+
+// Every split on a constant slot of the compact scoring vector decided here, once: the pipelined stream's rows
+// carry 0.5 in slots 12, 24, 25, 33, 34 and 0 in the other 37 that are not among the 22 varying ones (compact_src),
+// so such a node sends every transaction the same way — left iff value < threshold in f32, pack_forest_host's
+// comparison (the constants are never NaN: default_left plays no part) — and it is replaced by that child. Nodes are
+// renumbered in pre-order; leaf values and the tree order are untouched. A tree that resolves to one leaf becomes a
+// root over two leaves of that value (slot 0 against 0, never looked at); a tree that was a lone leaf stays one.
+ContractedForest contract_forest_host(const fd_forest_params& p, const fd_tree_arrays& t) {
+  FD_REQUIRE(p.kind == FD_FOREST_XGB_BINARY_LOGISTIC || p.kind == FD_FOREST_SKLEARN_IFOREST, FD_ERR_INVALID_ARG,
+             "contraction: XGBoost binary:logistic or IsolationForest trees");
+  FD_REQUIRE(p.num_feature > 0 && p.num_feature <= kMaxFeatures, FD_ERR_UNSUPPORTED, "num_feature must be in [1, 64]");
+  FD_REQUIRE(forest_depth_probe(t) >= 0, FD_ERR_INVALID_ARG, "incomplete tree arrays or a tree that is not a tree");
+  const bool xgb = p.kind == FD_FOREST_XGB_BINARY_LOGISTIC;
+  ContractedForest c;
+  c.off.push_back(0);
+  struct Item {
+    int32_t o, lo, ro;  // node, its children after resolution (original ids)
+    int depth;
+  };
+  std::vector<Item> st, keep;
+  std::vector<int32_t> remap;
+  for (int i = 0; i < t.n_trees; ++i) {
+    const int64_t a = t.tree_offsets[i], m = t.tree_offsets[i + 1] - a;
+    const int32_t *L = t.left + a, *R = t.right + a, *F = t.feature + a;
+    auto resolve = [&](int32_t o) {  // down through the constant splits
+      while (L[o] >= 0) {
+        FD_REQUIRE(F[o] >= 0 && F[o] < p.num_feature, FD_ERR_INVALID_ARG, "split feature outside [0, num_feature)");
+        const int src = compact_src(F[o]);
+        if (src >= 0) break;
+        const float val = src == -2 ? 0.5f : 0.0f;
+        const float thr = xgb ? (float)t.threshold[a + o] : sklearn_threshold_to_lt(t.threshold[a + o]);
+        o = val < thr ? L[o] : R[o];
+      }
+      return o;
+    };
+    const int64_t base = (int64_t)c.left.size();
+    auto emit = [&](int32_t l, int32_t r, int32_t f, double thr, uint8_t dl, double leaf) {
+      c.left.push_back(l);
+      c.right.push_back(r);
+      c.feature.push_back(f);
+      c.threshold.push_back(thr);
+      c.dleft.push_back(dl);
+      c.leaf.push_back(leaf);
+      return (int32_t)((int64_t)c.left.size() - 1 - base);
+    };
+    int64_t splits_in = 0, splits_out = 0;
+    for (int64_t o = 0; o < m; ++o) splits_in += L[o] >= 0 ? 1 : 0;
+    int depth = 0;
+    const int32_t root = resolve(0);
+    if (L[root] < 0 && L[0] >= 0) {  // resolved entirely
+      emit(1, 2, 0, 0.0, 0, 0.0);
+      emit(-1, -1, 0, 0.0, 0, t.leaf_value[a + root]);
+      emit(-1, -1, 0, 0.0, 0, t.leaf_value[a + root]);
+      depth = 1;
+    } else {
+      // the surviving nodes keep their relative order (the root first), so a tree with nothing to resolve comes back
+      // as it went in
+      st.clear();
+      st.push_back({root, 0, 0});
+      keep.clear();
+      while (!st.empty()) {
+        Item it = st.back();
+        st.pop_back();
+        depth = std::max(depth, it.depth);
+        if (L[it.o] >= 0) {
+          it.lo = resolve(L[it.o]);
+          it.ro = resolve(R[it.o]);
+          st.push_back({it.ro, 0, 0, it.depth + 1});
+          st.push_back({it.lo, 0, 0, it.depth + 1});
+        }
+        keep.push_back(it);
+      }
+      std::sort(keep.begin() + 1, keep.end(), [](const Item& x, const Item& y) { return x.o < y.o; });
+      remap.assign((size_t)m, -1);
+      for (size_t k = 0; k < keep.size(); ++k) remap[(size_t)keep[k].o] = (int32_t)k;
+      for (const Item& it : keep) {
+        const int32_t o = it.o;
+        if (L[o] < 0) {
+          emit(-1, -1, F[o], t.threshold[a + o], t.default_left ? t.default_left[a + o] : 0, t.leaf_value[a + o]);
+        } else {
+          ++splits_out;
+          emit(remap[(size_t)it.lo], remap[(size_t)it.ro], F[o], t.threshold[a + o],
+               t.default_left ? t.default_left[a + o] : 0, t.leaf_value[a + o]);
+        }
+      }
+    }
+    c.pruned += splits_in - splits_out;
+    c.depth.push_back(std::max(depth, 1));
+    c.off.push_back((int64_t)c.left.size());
+  }
+  return c;
 }
 
 namespace {
@@ -97,7 +193,7 @@ struct EnsArgs {
   int owner_fixed;                // chunk owner: tree group 0 (the oldest waves: highest issue priority), else rotating
   int prio;                       // issue priority 2 above the co-running feature kernels (engine option ensemble_prio)
   int n_pass;
-  int pad0;
+  int ldepth;                      // variable-depth walk (VD kernels): the plan's depth D, leaf rows of 2^D values
   unsigned long long pass_global;  // bit p: pass p bins from global memory (its table does not fit LDS)
   const char* img;                 // the passes' padded table images (thr_pad layout), 1 KiB pieces
   const char* nodes[2];
@@ -199,12 +295,114 @@ __device__ __forceinline__ unsigned long long walk_pack(uint32_t cur, int gg, ui
   return ((unsigned long long)hi << 32) | lo;
 }
 
+// The walk over contracted trees (build_plan: every split on a constant slot of the compact vector resolved on the
+// host), tree j a perfect heap of its own depth d[j] <= 8, the depths wave-uniform (SGPRs). Level-synchronous: the
+// selects of all chains first (VALU only; a finished chain's select is dead), then the reads of the chains that go on
+// — chain j issues its bin read only while l + 1 < d[j] and its pair read while l + 2 < d[j] — so the uniform branches
+// stand between whole phases and not inside a chain's step. The leaf index is formed at level d[j] - 1.
+template <int TPG, bool NAN_AWARE>
+__device__ __forceinline__ void walk_ens_var(uint32_t buf, int t0, uint32_t lane4, const int (&d)[TPG],
+                                             uint32_t (&leaf)[TPG]) {
+  uint32_t tb[TPG], node[TPG], kl[TPG], kr[TPG], xw[TPG];
+  int dw = 1;
+#pragma unroll
+  for (int j = 0; j < TPG; ++j) {
+    tb[j] = buf + (uint32_t)(t0 + j) * 1024u;
+    asm volatile("" : "+v"(tb[j]));
+    node[j] = lds_load<uint32_t>(tb[j] + 4u);
+    dw = max(dw, d[j]);
+    leaf[j] = 0u;
+  }
+#pragma unroll
+  for (int j = 0; j < TPG; ++j) {
+    xw[j] = lds_load<uint16_t>((node[j] & 0xFC02u) | lane4);
+    const u32x2 k = lds_load<u32x2>(tb[j] + 8u);  // (a depth-1 tree's: inside its block, unused)
+    kl[j] = k.x;
+    kr[j] = k.y;
+  }
+#pragma unroll
+  for (int l = 0; l < 8; ++l) {
+    if (l >= dw) break;
+#pragma unroll
+    for (int j = 0; j < TPG; ++j) {
+      bool right = xw[j] > (node[j] >> 16);
+      if (NAN_AWARE) {
+        if (xw[j] == 0xFFFFu) right = (node[j] & 1u) == 0u;
+      }
+      const uint32_t at = ((node[j] & kLinkMask) >> 2) + (right ? 1u : 0u);
+      leaf[j] = (l + 1 == d[j]) ? at : leaf[j];
+      node[j] = right ? kr[j] : kl[j];
+    }
+    if (l + 1 >= dw) break;
+#pragma unroll
+    for (int j = 0; j < TPG; ++j) {
+      if (l + 1 < d[j]) {
+        xw[j] = lds_load<uint16_t>((node[j] & 0xFC02u) | lane4);
+        if (l + 2 < d[j]) {
+          const u32x2 k = lds_load<u32x2>((node[j] & kLinkMask) | tb[j]);
+          kl[j] = k.x;
+          kr[j] = k.y;
+        }
+      }
+    }
+  }
+}
+
+// walk_pack over a chunk of contracted trees: the wave's TPG depths from heap slot 0 of its trees' node blocks (one
+// broadcast read each, kept scalar). VD 1: every tree to its own depth (walk_ens_var); VD 2: the host padded the
+// wave's trees to the deepest of them, and that depth selects a fixed-depth walk_ens.
+template <int VD, int TPG>
+__device__ __forceinline__ unsigned long long walk_pack_var(uint32_t cur, int gg, uint32_t lane4, bool tile_nan) {
+  static_assert(TPG <= 8, "a byte per tree in a u64");
+  uint32_t leaf[TPG];
+  int d[TPG];
+#pragma unroll
+  for (int j = 0; j < TPG; ++j)
+    d[j] = __builtin_amdgcn_readfirstlane((int)lds_load<uint32_t>(cur + (uint32_t)(gg * TPG + j) * 1024u)) & 0xFF;
+  if (VD == 1) {
+    if (tile_nan)
+      walk_ens_var<TPG, true>(cur, gg * TPG, lane4, d, leaf);
+    else
+      walk_ens_var<TPG, false>(cur, gg * TPG, lane4, d, leaf);
+  } else {
+#define FD_WALK_DEPTH(K)                                          \
+  case K:                                                         \
+    if (tile_nan)                                                 \
+      walk_ens<K, TPG, true>(cur, gg * TPG, lane4, leaf);         \
+    else                                                          \
+      walk_ens<K, TPG, false>(cur, gg * TPG, lane4, leaf);        \
+    break;
+    switch (d[0]) {
+      FD_WALK_DEPTH(1)
+      FD_WALK_DEPTH(2)
+      FD_WALK_DEPTH(3)
+      FD_WALK_DEPTH(4)
+      FD_WALK_DEPTH(5)
+      FD_WALK_DEPTH(6)
+      FD_WALK_DEPTH(7)
+      default:
+        if (tile_nan)
+          walk_ens<8, TPG, true>(cur, gg * TPG, lane4, leaf);
+        else
+          walk_ens<8, TPG, false>(cur, gg * TPG, lane4, leaf);
+        break;
+    }
+#undef FD_WALK_DEPTH
+  }
+  uint32_t lo = 0, hi = 0;
+#pragma unroll
+  for (int j = 0; j < TPG; ++j) {
+    if (j < 4) lo |= leaf[j] << (8 * j);
+    else hi |= leaf[j] << (8 * (j - 4));
+  }
+  return ((unsigned long long)hi << 32) | lo;
+}
+
 // One transaction's share of a finished chunk: its CH leaf values (indices from the tile, values from the
 // chunk's leaf block in LDS) added in tree order to the forest's running sum — the reference's sequential
 // f32 margin / f64 path-length sum, bit for bit.
 template <int D, int TPG, int CH, typename LeafT>
-__device__ __forceinline__ void owner_sum(uint32_t buf, uint32_t tile, uint32_t acc, int txn) {
-  constexpr int NL = 1 << D;
+__device__ __forceinline__ void owner_sum(uint32_t buf, uint32_t tile, uint32_t acc, int txn, const int NL = 1 << D) {
   unsigned long long w[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) w[q] = lds_load<unsigned long long>(tile + (uint32_t)(q * kTile + txn) * 8u);
@@ -481,7 +679,8 @@ __device__ __forceinline__ void bin_compact_pass(const EnsArgs& a, const float (
   }
 }
 
-template <int D, int OUT, bool WIDE, bool LUT = true>
+// VD != 0 (D = 8): the chunks hold contracted trees of their own depths (walk_pack_var), leaf rows of 2^a.ldepth
+template <int D, int OUT, bool WIDE, bool LUT = true, int VD = 0>
 __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
   constexpr int kCHA = EnsCfg<WIDE>::CHA, kCHB = EnsCfg<WIDE>::CHB;
   constexpr uint32_t kEnsBuf = EnsCfg<WIDE>::BUF;
@@ -501,6 +700,7 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
   const int64_t row = (int64_t)blockIdx.x * kTile + txn;
   const bool valid = row < a.n;
   const int nA = a.n_chunks[0], G = nA + a.n_chunks[1];
+  const int NL = VD ? 1 << a.ldepth : 1 << D;  // leaf values per tree row
 
 #ifdef FD_FOREST_PROFILE
   unsigned long long pr_top = 0, pr_walk = 0, pr_sync = 0, pr_dma = 0, pr_st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -707,8 +907,8 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
       if (g > 0) {
         const int c = g - 1;
         const uint32_t bp = (c & 1) ? bufB : bufA, tp = (c & 1) ? tile1 : tile0;
-        if (c < nA) owner_sum<D, TPGA, kCHA, float>(bp, tp, accA, txn);
-        else owner_sum<D, TPGB, kCHB, double>(bp, tp, accB, txn);
+        if (c < nA) owner_sum<D, TPGA, kCHA, float>(bp, tp, accA, txn, NL);
+        else owner_sum<D, TPGB, kCHB, double>(bp, tp, accB, txn, NL);
         // the leaf reads of all four owner waves are complete before any of them overwrites the buffer
         if (lane == 0)
           __hip_atomic_fetch_add(reinterpret_cast<uint32_t*>(lbase + (owner_cnt - s0)), 1u, __ATOMIC_RELAXED,
@@ -725,8 +925,11 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
     }
     const uint32_t cur = (g & 1) ? bufB : bufA, tw = (g & 1) ? tile1 : tile0;
     FD_ESTAMP(q1);
-    const unsigned long long w =
-        g < nA ? walk_pack<D, TPGA>(cur, gg, lane4, tile_nan) : walk_pack<D, TPGB>(cur, gg, lane4, tile_nan);
+    unsigned long long w;
+    if (VD)
+      w = g < nA ? walk_pack_var<VD, TPGA>(cur, gg, lane4, tile_nan) : walk_pack_var<VD, TPGB>(cur, gg, lane4, tile_nan);
+    else
+      w = g < nA ? walk_pack<D, TPGA>(cur, gg, lane4, tile_nan) : walk_pack<D, TPGB>(cur, gg, lane4, tile_nan);
     lds_store<unsigned long long>(tw + (uint32_t)(gg * kTile + txn) * 8u, w);
     FD_ESTAMP(q2);
     if (owner) dma_wait();
@@ -745,8 +948,8 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
   if (G > 0 && gg == (a.owner_fixed ? 0 : ((G - 1) & 3))) {
     const int c = G - 1;
     const uint32_t bp = (c & 1) ? bufB : bufA, tp = (c & 1) ? tile1 : tile0;
-    if (c < nA) owner_sum<D, TPGA, kCHA, float>(bp, tp, accA, txn);
-    else owner_sum<D, TPGB, kCHB, double>(bp, tp, accB, txn);
+    if (c < nA) owner_sum<D, TPGA, kCHA, float>(bp, tp, accA, txn, NL);
+    else owner_sum<D, TPGB, kCHB, double>(bp, tp, accB, txn, NL);
   }
   __syncthreads();
 #ifdef FD_FOREST_PROFILE
@@ -841,6 +1044,17 @@ const void* pick_ensemble(int out, bool wide, int D) {
   return out == 1 ? pick_ensemble<1, false>(D) : out == 2 ? pick_ensemble<2, false>(D) : pick_ensemble<0, false>(D);
 }
 
+// the variable-depth instantiations (contracted chunks; blended columns or route records only: compact rows are the
+// pipelined stream's), walk_pack_var's VD: 1 per tree / 2 per wave
+const void* pick_ensemble_var(int out, bool wide, int vd) {
+  if (vd == 2) {
+    if (wide) return out == 1 ? (const void*)ensemble_kernel<8, 1, true, true, 2> : (const void*)ensemble_kernel<8, 0, true, true, 2>;
+    return out == 1 ? (const void*)ensemble_kernel<8, 1, false, true, 2> : (const void*)ensemble_kernel<8, 0, false, true, 2>;
+  }
+  if (wide) return out == 1 ? (const void*)ensemble_kernel<8, 1, true, true, 1> : (const void*)ensemble_kernel<8, 0, true, true, 1>;
+  return out == 1 ? (const void*)ensemble_kernel<8, 1, false, true, 1> : (const void*)ensemble_kernel<8, 0, false, true, 1>;
+}
+
 fd_tree_arrays arrays_of(const PackedForest& f) {
   fd_tree_arrays t{};
   t.n_trees = f.n_trees;
@@ -887,7 +1101,8 @@ void plan_passes(const std::vector<float>& thr, const std::vector<int32_t>& off,
 
 // joint repack of forest A (XGBoost, slot sa) and B (IsolationForest, slot sb) into plan P; either slot may be -1
 // (a single forest: the kernel walks only the other one); false when not possible (the per-model path runs)
-bool build_plan(Engine& e, EnsemblePlan& P, int sa, int sb, bool wide) {
+// contract (option ensemble_contract; 0 for the single-forest plans, whose rows are 64-wide): also pack nodes_c[]
+bool build_plan(Engine& e, EnsemblePlan& P, int sa, int sb, bool wide, int contract = 0) {
   P.valid = false;
   const PackedForest* F[2] = {sa >= 0 ? &e.forests[sa] : nullptr, sb >= 0 ? &e.forests[sb] : nullptr};
   if (!F[0] && !F[1]) return false;
@@ -974,6 +1189,74 @@ bool build_plan(Engine& e, EnsemblePlan& P, int sa, int sb, bool wide) {
     P.n_chunks[k] = nc;
     P.stride[k] = stride;
   }
+  // The contracted forests (contract_forest_host) in the same chunk geometry: tree i a perfect heap of depth dw <= D —
+  // the deepest of its wave's TPG trees (contract 1) or its own depth d_i (contract 2) — in its 1 KiB node block, the
+  // last split level's link s - 2^(dw - 1), dw in heap slot 0 (it arrives with the chunk's DMA), its 2^dw leaves at
+  // the start of its leaf row [2^D]. Padding trees of a partial last chunk: pad nodes and zero leaves (contract 2:
+  // depth 1). Thresholds are looked up in the same merged tables (the contracted trees' are a subset).
+  P.contract = contract;
+  P.contracted = false;
+  P.nodes_pruned = 0;
+  P.steps_full = P.steps_c = 0;
+  for (int k = 0; k < 2 && contract; ++k) {
+    if (!F[k]) continue;
+    const bool xgb = F[k]->params.kind == FD_FOREST_XGB_BINARY_LOGISTIC;
+    const ContractedForest c = contract_forest_host(F[k]->params, arrays_of(*F[k]));
+    const int T = hp[k].n_trees, nc = P.n_chunks[k], ch = CH[k], tpg = ch / 4;
+    const size_t nb = (size_t)nc * ch;
+    std::vector<int> dw(nb, 1);
+    for (int i = 0; i < T; ++i) dw[i] = std::min(c.depth[i], D);
+    if (contract == 1)
+      for (size_t g0 = 0; g0 < nb; g0 += tpg) {
+        const int mx = *std::max_element(dw.begin() + g0, dw.begin() + g0 + tpg);
+        std::fill(dw.begin() + g0, dw.begin() + g0 + tpg, mx);
+      }
+    std::vector<char> blob((size_t)nc * P.stride[k], 0);
+    std::vector<int32_t> cur(2 * NL);
+    for (size_t i = 0; i < nb; ++i) {
+      char* chunk = blob.data() + (i / ch) * P.stride[k];
+      uint32_t* dst = reinterpret_cast<uint32_t*>(chunk + (i % ch) * 1024);
+      dst[0] = (uint32_t)dw[i];
+      const int nl = 1 << dw[i];
+      if ((int)i >= T) {  // a padding tree: pad nodes with their links (a zero word would link to heap slot 0)
+        for (int s = 1; s < nl; ++s) dst[s] = (s < (nl >> 1) ? (uint32_t)s : (uint32_t)(s - (nl >> 1))) << 3;
+        continue;
+      }
+      P.steps_c += dw[i];
+      const int64_t a = c.off[i];
+      cur[1] = 0;
+      for (int s = 1; s < nl; ++s) {
+        const int32_t o = cur[s];
+        const uint32_t link = s < (nl >> 1) ? (uint32_t)s : (uint32_t)(s - (nl >> 1));
+        if (c.left[a + o] < 0) {  // a leaf above depth dw: pad node, both ways reach it
+          dst[s] = link << 3;
+          cur[2 * s] = cur[2 * s + 1] = o;
+          continue;
+        }
+        const uint32_t f = (uint32_t)c.feature[a + o];
+        const float thr = xgb ? (float)c.threshold[a + o] : sklearn_threshold_to_lt(c.threshold[a + o]);
+        const uint32_t jm = (uint32_t)(std::lower_bound(merged[f].begin(), merged[f].end(), thr) - merged[f].begin());
+        dst[s] = (jm << 16) | ((f >> 1) << 10) | (link << 3) | ((f & 1u) << 1) | (c.dleft[a + o] ? 1u : 0u);
+        cur[2 * s] = c.left[a + o];
+        cur[2 * s + 1] = c.right[a + o];
+      }
+      char* leaves = chunk + (size_t)ch * 1024 + (i % ch) * NL * leaf_sz[k];
+      for (int s = 0; s < nl; ++s) {
+        const double v = c.leaf[a + cur[nl + s]];
+        if (k == 0) {
+          const float vf = (float)v;
+          std::memcpy(leaves + (size_t)s * 4, &vf, 4);
+        } else {
+          std::memcpy(leaves + (size_t)s * 8, &v, 8);
+        }
+      }
+    }
+    P.nodes_c[k].ensure(blob.size());
+    FD_HIP(hipMemcpy(P.nodes_c[k].ptr, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    P.nodes_pruned += c.pruned;
+  }
+  for (int k = 0; k < 2; ++k) P.steps_full += F[k] ? (long long)hp[k].n_trees * D : 0;
+  P.contracted = contract != 0 && P.steps_c < P.steps_full;
   P.thr.ensure(std::max<size_t>(4, thr.size() * sizeof(float)));
   if (!thr.empty()) FD_HIP(hipMemcpy(P.thr.ptr, thr.data(), thr.size() * sizeof(float), hipMemcpyHostToDevice));
   P.h_thr_off = off;
@@ -1020,8 +1303,8 @@ bool build_plan(Engine& e, EnsemblePlan& P, int sa, int sb, bool wide) {
   return true;
 }
 
-bool plan_current(const Engine& e, const EnsemblePlan& P, int sa, int sb, bool wide) {
-  return P.valid && P.wide == wide && P.slot[0] == sa && P.slot[1] == sb &&
+bool plan_current(const Engine& e, const EnsemblePlan& P, int sa, int sb, bool wide, int contract = 0) {
+  return P.valid && P.wide == wide && P.contract == contract && P.slot[0] == sa && P.slot[1] == sb &&
          P.gen[0] == (sa >= 0 ? e.forests[sa].gen : 0) && P.gen[1] == (sb >= 0 ? e.forests[sb].gen : 0);
 }
 
@@ -1076,7 +1359,9 @@ bool select_pair(Engine& e, const fd_blend_params& p, const int32_t* slots, cons
   }
   if (q.sa < 0 || q.sb < 0) return false;
   const bool wide = want_wide(e);
-  if (!plan_current(e, e.ens, q.sa, q.sb, wide) && !build_plan(e, e.ens, q.sa, q.sb, wide)) return false;
+  if (!plan_current(e, e.ens, q.sa, q.sb, wide, e.ens_contract) &&
+      !build_plan(e, e.ens, q.sa, q.sb, wide, e.ens_contract))
+    return false;
   return true;
 }
 }  // namespace
@@ -1113,8 +1398,8 @@ void plan_args(const EnsemblePlan& P, const float* dX, int64_t n, int32_t ld, bo
 }
 
 // out: 0 blended columns, 1 route result records, 2 the single forest's probability column (a.fp)
-bool run_plan(Engine& e, const EnsemblePlan& P, EnsArgs& a, int out, int timing_kind) {
-  const void* fn = pick_ensemble(out, P.wide, P.D);
+bool run_plan(Engine& e, const EnsemblePlan& P, EnsArgs& a, int out, int timing_kind, int vd = 0) {
+  const void* fn = vd && out != 2 ? pick_ensemble_var(out, P.wide, vd) : pick_ensemble(out, P.wide, P.D);
   if (!fn) return false;
   const size_t lds = ens_lds(P.nf, P.wide);
   FD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1169,7 +1454,17 @@ bool launch_ensemble(Engine& e, const fd_blend_params& p, const int32_t* slots, 
   a.res = results;
   const int out = results ? 1 : 0;
   FD_REQUIRE(out == 1 || dfp != nullptr, FD_ERR_INVALID_ARG, "null output");
-  return run_plan(e, e.ens, a, out, FD_TIMING_ENSEMBLE);
+  // compact / split rows carry the constant slots' values by construction: the contracted chunks and the
+  // variable-depth walk, when the contraction shortened any tree; 64-wide rows keep nodes[] and the fixed-depth kernels
+  const int vd = (compact && e.ens.contracted) ? (e.ens.contract == 1 ? 2 : 1) : 0;  // walk_pack_var's VD
+  if (vd) {
+    for (int k = 0; k < 2; ++k) a.nodes[k] = e.ens.nodes_c[k].as<const char>();
+    a.ldepth = e.ens.D;
+  }
+  if (!run_plan(e, e.ens, a, out, FD_TIMING_ENSEMBLE, vd)) return false;
+  if (vd) ++e.ens_contract_total;
+  e.ens_steps_last = vd ? e.ens.steps_c : e.ens.steps_full;
+  return true;
 }
 
 bool launch_ensemble_single(Engine& e, int slot, const float* dX, int64_t n, int32_t ld, double* dprob,

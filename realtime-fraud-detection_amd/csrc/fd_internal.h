@@ -238,7 +238,40 @@ struct EnsemblePlan {
   DeviceBuffer img;    // every staged binning pass's padded table image (ensemble.hip plan_passes), LDS-DMA source
   EnsPassSet passes;
   int max_feature_thr = 0;
+  // the forests contracted against the compact vector's constant slots (ensemble.hip contract_forest_host): the same
+  // chunk geometry, tree t a perfect heap of its own depth d_t (heap slot 0 of its node block holds d_t), its 2^d_t
+  // leaves at the start of its leaf row. contract: the mode the plan was built for (option ensemble_contract: 0 none,
+  // 1 every tree padded to the deepest of its wave's trees, 2 every tree its own depth); contracted: some tree is
+  // walked over fewer than D levels (else the launches keep nodes[])
+  DeviceBuffer nodes_c[2];
+  int contract = 0;
+  bool contracted = false;
+  long long nodes_pruned = 0;           // splits of the loaded forests that the contracted ones no longer hold
+  long long steps_full = 0, steps_c = 0;  // node steps per transaction: n_trees x D over both forests / sum of d_t
 };
+
+// A forest with every split on a constant slot of the compact scoring vector (compact_src(f) < 0: the value 0.5 or 0)
+// replaced by the child that value takes — left iff value < threshold in f32, the packer's comparison — ensemble.hip
+struct ContractedForest {
+  std::vector<int64_t> off;
+  std::vector<int32_t> left, right, feature, depth;  // depth: per tree, >= 1 (a lone leaf walks one pad level)
+  std::vector<double> threshold, leaf;
+  std::vector<uint8_t> dleft;
+  long long pruned = 0;
+  fd_tree_arrays arrays() const {
+    fd_tree_arrays t{};
+    t.n_trees = (int32_t)off.size() - 1;
+    t.tree_offsets = off.data();
+    t.left = left.data();
+    t.right = right.data();
+    t.feature = feature.data();
+    t.threshold = threshold.data();
+    t.default_left = dleft.data();
+    t.leaf_value = leaf.data();
+    return t;
+  }
+};
+ContractedForest contract_forest_host(const fd_forest_params& p, const fd_tree_arrays& t);
 
 // card-hash routing records (route.hip): one transaction (48 B) / one result (24 B)
 struct __attribute__((aligned(16))) RouteRecord {
@@ -692,6 +725,10 @@ struct Engine {
   int forest_variant = 0;  // "forest_kernel" option
   bool ens_owner_fixed = true;  // "ensemble_owner" option (A/B of the fused kernel's chunk-owner schedule)
   int ens_chunks = 0;           // "ensemble_chunks": 0 auto, 1 wide, 2 compact chunk layout (ensemble.hip)
+  int ens_contract = 1;         // "ensemble_contract": compact / split rows walk the forests contracted against the
+                                // constant slots: 0 no, 1 (default) each tree to its wave's deepest, 2 to its own depth
+  unsigned long long ens_contract_total = 0;  // counter "ensemble_contracted_launches"
+  long long ens_steps_last = 0;  // counter "ensemble_node_steps_per_txn": node steps per transaction of the last fused launch
   int mlp_form = 0;        // "mlp_form" option: 0 auto, 1 the LDS form (mlp_lds_kernel) for the reference shape too
   int mlp_wgs_per_cu = 0;  // "mlp_wgs_per_cu" option: the MLP's persistent grid, workgroups per CU (0 auto: 2 where they fit)
   int lstm_rows = 0;  // "lstm_rows" option: transactions per LSTM workgroup tile (0 auto, 4 or 16)

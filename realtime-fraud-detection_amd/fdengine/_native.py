@@ -406,6 +406,8 @@ SIGNATURES = {
     "fd_timing_reset": (C.c_int, [_vp]),
     "fd_pack_forest_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), _vp, _i64, _vp, _i64,
                                       C.POINTER(fd_pack_info)]),
+    "fd_contract_forest_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), C.POINTER(_i64),
+                                          C.POINTER(fd_tree_arrays), C.POINTER(C.c_int32), C.POINTER(_i64)]),
     "fd_pack_forest_binned_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), _vp, _i64,
                                              _vp, _i64, _vp, C.POINTER(fd_pack_info)]),
     "fd_pack_forest_sparse_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), _vp, _i64,

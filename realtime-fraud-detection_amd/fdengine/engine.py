@@ -816,6 +816,28 @@ def pack_forest_host(fa: ForestArrays):
     return blob.tobytes(), ids, info
 
 
+def contract_forest_host(fa: ForestArrays):
+    """Host-only (no GPU): the forest with every split on a constant slot of the compact scoring vector resolved
+    (fd_contract_forest_host) -> (ForestArrays, depths int32 [n_trees], splits pruned)."""
+    p, t, keep = fa.c_structs()
+    nn, pruned = C.c_int64(), C.c_int64()
+    N.call("fd_contract_forest_host", C.byref(p), C.byref(t), C.byref(nn), None, None, None)
+    T, M = fa.n_trees, nn.value
+    out = ForestArrays(kind=fa.kind, num_feature=fa.num_feature, offsets=np.zeros(T + 1, np.int64),
+                       left=np.zeros(M, np.int32), right=np.zeros(M, np.int32), feature=np.zeros(M, np.int32),
+                       threshold=np.zeros(M, np.float64), default_left=np.zeros(M, np.uint8),
+                       leaf_value=np.zeros(M, np.float64), base_score=fa.base_score, if_offset=fa.if_offset,
+                       if_denominator=fa.if_denominator)
+    _, to, ko = out.c_structs()
+    depths = np.zeros(T, np.int32)
+    N.call("fd_contract_forest_host", C.byref(p), C.byref(t), C.byref(nn), C.byref(to),
+           depths.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(pruned))
+    del keep
+    for name in ("offsets", "left", "right", "feature", "threshold", "default_left", "leaf_value"):
+        setattr(out, name, ko[name])
+    return out, depths, pruned.value
+
+
 def pack_forest_binned_host(fa: ForestArrays):
     """Host-only binned repack (no GPU): -> (blob bytes, thresholds f32, offsets int32, fd_pack_info).
     Raises NativeError(FD_ERR_UNSUPPORTED) when a feature has more than 65534 distinct thresholds."""
