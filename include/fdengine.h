@@ -190,6 +190,43 @@ int fd_pack_forest_binned_host(const fd_forest_params* params, const fd_tree_arr
 int fd_contract_forest_host(const fd_forest_params* params, const fd_tree_arrays* trees, int64_t* n_nodes,
                             fd_tree_arrays* out, int32_t* depths, int64_t* n_pruned);
 
+/* Host-only: the dense chunk layout of one contracted forest, as the fused kernel walks it on compact / split rows
+   under ensemble_contract 3 and 4 (the engine's plan is built by the same function, against the two forests' merged
+   threshold tables; here the tables are the forest's own). XGBoost and IsolationForest kinds, contracted depth <= 8.
+   Bundles: trees_per_bundle trees walked by one wave (wide 6 XGBoost / 4 IsolationForest, compact 5 / 3), every tree
+   of a bundle a perfect 1-based heap of the bundle's depth d = the deepest of its trees. mode 3: tree i of the forest
+   in bundle i / trees_per_bundle; mode 4: the chunk's trees sorted by depth (deepest first, forest order among
+   equals), then cut into bundles, a partial bundle (the forest's last chunk) at the last
+   place where the sum of the walked depths is least. A chunk is a run of consecutive trees, grown a bundle's worth of trees at a time
+   while it holds at most s_max bundles and its data fit buf_bytes. Its bundles go to the four tree groups deepest
+   first, each to the group with the least sum of depths so far (the lowest group on ties; group 0 starts at
+   owner_bias / 16 levels per tree of the chunk, 0 = none).
+   Chunk image: node blocks (largest first), then leaf rows (forest order), zero-padded to 1 KiB; then the 1 KiB chunk
+   table. A tree's node block is 4 * 2^d bytes, aligned to its size: word s (1 <= s < 2^d) is heap slot s,
+     threshold index << 16 | (slot >> 1) << 10 | link << 3 | (slot & 1) << 1 | default_left
+   slot = the feature's index among the 22 varying slots (0, 1, 5, 6, 7, 14, 15, 16, 17, 19, 21, 23, 26, 27, 31, 32,
+   41..46), threshold index j into the feature's ascending table: left iff bin(x) <= j, bin(x) = #{t <= x}, NaN:
+   default_left. link = s above the last split level (the children are words 2 s, 2 s + 1), s - 2^(d-1) on it: the leaf
+   index is 2 link + right. A node below a leaf is a pad (threshold index 0, slot 0): both ways reach that leaf's
+   value. Its leaf row is 2^d values (f32 XGBoost, f64 IsolationForest). The free slots of a partial last bundle repeat
+   its first tree's block. Chunk table, u32 words: [0] trees | bundles << 8; [1], [2] the next chunk's offset and
+   length in KiB (0, 0 after the last); [3] bundles of tree group g in byte g; at byte 64 + 128 g + 16 i the i-th
+   bundle of group g: {d | bundle << 8 | g << 16, then six u16 node-block offsets}; at byte 576 + 4 k the chunk's k-th
+   tree (forest order): leaf-index byte (2048 bundle + place in the bundle) | leaf-row offset << 16.
+   Call with blob == NULL for info, then with blob (info->blob_bytes), chunk_offsets / chunk_lengths (info->n_chunks),
+   tree_info (n_trees), thresholds (info->n_thresholds) and thr_offsets (num_feature + 1); any may be NULL. */
+typedef struct fd_dense_tree {
+  int32_t chunk, bundle, group, depth;  /* bundle: index in its chunk; depth: as walked */
+  int32_t node_offset, leaf_offset;     /* bytes from the chunk's start */
+} fd_dense_tree;
+typedef struct fd_dense_info {
+  int32_t n_chunks, s_max, trees_per_bundle, buf_bytes;
+  int64_t blob_bytes, n_thresholds, node_steps; /* node_steps: the sum of the trees' walked depths */
+} fd_dense_info;
+int fd_dense_layout_host(const fd_forest_params* params, const fd_tree_arrays* trees, int32_t wide, int32_t mode,
+                         int32_t owner_bias, fd_dense_info* info, void* blob, int64_t* chunk_offsets,
+                         int32_t* chunk_lengths, fd_dense_tree* tree_info, float* thresholds, int32_t* thr_offsets);
+
 /* Sparse (pointer) layout, host-only repack: trees of ANY depth and any kind keep their shape (no padding). It is the
    only layout of FD_FOREST_SKLEARN_PROBA and of forests deeper than 10 levels (fd_load_forest picks it for them;
    fd_forest_info then reports the true depth), and what engine option forest_kernel = 11 walks for any forest.
@@ -931,8 +968,12 @@ int fd_engine_set_timing(fd_engine* eng, int enable);
      communicators (fd_comm_init), else wide; 1 wide (24 XGBoost / 16 IsolationForest trees per chunk, 148 KB of
      LDS); 2 compact (20 / 12, 132 KB: room for an RCCL kernel on the same CU). Outputs are identical.
      "ensemble_contract": the fused kernel on the pipelined stream's compact / split rows walks the forests contracted
-     against the rows' constant slots (fd_contract_forest_host): 1 (default) each tree to the deepest of its wave's
-     trees, 2 each tree to its own depth (slower: an A/B option), 0 the full forests. Outputs are identical.
+     against the rows' constant slots (fd_contract_forest_host): 4 (default) the dense chunk stream of
+     fd_dense_layout_host — trees as perfect heaps of their bundle's depth in blocks of their own size, up to 8
+     bundles per chunk and barrier, the bundles dealt to the tree groups by depth — with a chunk's trees sorted by
+     depth before they are cut into bundles; 3 the same with bundles of consecutive trees; 1 the padded chunks, each
+     tree to the deepest of its wave's trees; 2 each tree to its own depth (slower); 0 the full forests (1, 2, 0: A/B
+     options). Outputs are identical.
      "lstm_rows": LSTM tile, 0 auto (4 transactions below 4096, else 16), 4 or 16
      "mlp_form": the MLP head's kernel for the reference shape (3 layers, padded widths 64): 0 (default) weights in
      registers, 1 the LDS form every other shape takes
@@ -981,7 +1022,8 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    the compact 64-B rows: no vectors requested), "ensemble_single_launches" (fd_forest_predict batches scored by the
    fused kernel over one forest), "ensemble_contracted_launches" (fused launches over the contracted forests),
    "ensemble_nodes_pruned" (splits the current plan's contraction removed), "ensemble_node_steps_per_txn" (tree levels
-   walked per transaction by the last fused pair launch), "forest_sparse_launches" (launches of the sparse-layout forest kernel),
+   walked per transaction by the last fused pair launch), "ensemble_dense_chunks" (chunks of that launch over both
+   forests when it walked the dense chunk stream, else 0), "forest_sparse_launches" (launches of the sparse-layout forest kernel),
    "mlp_launches" (launches of the MLP head's kernel), "graph_steps" (fd_graph_step_* calls with n > 0),
    "text_calls" (fd_text_features_device / _host calls with n > 0), "text_nonascii_rows" (rows those calls flagged
    FD_TEXT_NONASCII; reading it waits for the engine stream),

@@ -589,6 +589,9 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
   } else if (k == "ensemble_node_steps_per_txn") {  // the last fused pair launch: tree levels walked per transaction
     // over both forests (the sum of the depths as walked; n_trees x D on the uncontracted path)
     *value = (int64_t)e.ens_steps_last;
+  } else if (k == "ensemble_dense_chunks") {  // the last fused pair launch: chunks over both forests when it walked the
+    // dense chunk stream (ensemble_contract 3 / 4), else 0
+    *value = (int64_t)e.ens_dense_chunks_last;
   } else if (k == "forest_sparse_launches") {  // launches of forest_sparse_kernel: predict_proba forests, forests
     // deeper than 10 levels, and any forest under option forest_kernel = 11
     *value = (int64_t)e.sparse_total;
@@ -666,11 +669,13 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value) {
     FD_REQUIRE(value >= 0 && value <= 2, FD_ERR_INVALID_ARG, "ensemble_chunks must be 0, 1 or 2");
     e.ens_chunks = (int)value;
   } else if (k == "ensemble_contract") {  // fused kernel on compact / split rows: the forests contracted against the
-    // rows' constant slots (ensemble.hip contract_forest_host) and walked to 1 (default) the deepest of each wave's
-    // trees (a fixed-depth walk chosen per wave and chunk), 2 each tree's own depth (uniform branches inside the walk:
-    // measured slower); 0 the full forests at the common depth (outputs identical in every mode). A change
-    // rebuilds the plan's chunks: the device is idle first
-    FD_REQUIRE(value >= 0 && value <= 2, FD_ERR_INVALID_ARG, "ensemble_contract must be 0, 1 or 2");
+    // rows' constant slots (ensemble.hip contract_forest_host). 4 (default) / 3: the contracted trees packed densely,
+    // up to eight bundles per chunk and barrier (dense_layout_host), bundles of the chunk's trees sorted by depth / of
+    // consecutive trees; 1 the padded chunks, each tree walked to the deepest of its wave's trees (a fixed-depth walk
+    // chosen per wave and chunk); 2 each tree's own depth (uniform branches inside the walk: measured slower, DESIGN
+    // §3); 0 the full forests at the common depth. Outputs are identical in every mode. A change rebuilds the plan's
+    // chunks: the device is idle first
+    FD_REQUIRE(value >= 0 && value <= 4, FD_ERR_INVALID_ARG, "ensemble_contract must be 0 .. 4");
     if ((int)value != e.ens_contract) {
       e.activate();
       FD_HIP(hipDeviceSynchronize());
@@ -888,6 +893,46 @@ int fd_contract_forest_host(const fd_forest_params* params, const fd_tree_arrays
     std::memcpy(const_cast<double*>(out->threshold), c.threshold.data(), (size_t)M * 8);
     std::memcpy(const_cast<uint8_t*>(out->default_left), c.dleft.data(), (size_t)M);
     std::memcpy(const_cast<double*>(out->leaf_value), c.leaf.data(), (size_t)M * 8);
+  }
+  FD_API_END
+}
+
+int fd_dense_layout_host(const fd_forest_params* params, const fd_tree_arrays* trees, int32_t wide, int32_t mode,
+                         int32_t owner_bias, fd_dense_info* info, void* blob, int64_t* chunk_offsets,
+                         int32_t* chunk_lengths, fd_dense_tree* tree_info, float* thresholds, int32_t* thr_offsets) {
+  FD_API_BEGIN
+  FD_REQUIRE(params && trees && info, FD_ERR_INVALID_ARG, "null params/trees/info");
+  const fd::ContractedForest c = fd::contract_forest_host(*params, *trees);
+  const bool xgb = params->kind == FD_FOREST_XGB_BINARY_LOGISTIC;
+  // the forest's own tables: the distinct f32 thresholds of the contracted splits, per feature, ascending
+  std::vector<std::vector<float>> tables((size_t)params->num_feature);
+  for (size_t o = 0; o < c.left.size(); ++o)
+    if (c.left[o] >= 0)
+      tables[(size_t)c.feature[o]].push_back(xgb ? (float)c.threshold[o] : fd::sklearn_threshold_to_lt(c.threshold[o]));
+  int64_t n_thr = 0;
+  for (std::vector<float>& t : tables) {
+    std::sort(t.begin(), t.end());
+    t.erase(std::unique(t.begin(), t.end()), t.end());
+    n_thr += (int64_t)t.size();
+  }
+  const fd::DenseLayout L = fd::dense_layout_host(c, xgb, tables, wide != 0, mode, owner_bias);
+  info->n_chunks = (int32_t)L.chunk_len.size();
+  info->s_max = fd::kDenseSMax;
+  info->trees_per_bundle = L.tpg;
+  info->buf_bytes = (int32_t)L.buf;
+  info->blob_bytes = (int64_t)L.blob.size();
+  info->n_thresholds = n_thr;
+  info->node_steps = L.steps;
+  if (blob) std::memcpy(blob, L.blob.data(), L.blob.size());
+  if (chunk_offsets) std::memcpy(chunk_offsets, L.chunk_off.data(), L.chunk_off.size() * 8);
+  if (chunk_lengths) std::memcpy(chunk_lengths, L.chunk_len.data(), L.chunk_len.size() * 4);
+  if (tree_info) std::memcpy(tree_info, L.tree.data(), L.tree.size() * sizeof(fd_dense_tree));
+  if (thr_offsets) thr_offsets[0] = 0;
+  int64_t at = 0;
+  for (size_t f = 0; f < tables.size(); ++f) {
+    if (thresholds) std::memcpy(thresholds + at, tables[f].data(), tables[f].size() * 4);
+    at += (int64_t)tables[f].size();
+    if (thr_offsets) thr_offsets[f + 1] = (int32_t)at;
   }
   FD_API_END
 }

@@ -25,8 +25,20 @@
 // result records of the owner GPU).
 //
 // Compact / split rows (the pipelined stream) hold 42 constant slots: the plan also packs the forests with every
-// split on such a slot decided (contract_forest_host), and the VD instantiations walk each wave's trees only to the
-// deepest of them (walk_pack_var; engine option ensemble_contract). 64-wide rows keep the full forests.
+// split on such a slot decided (contract_forest_host); 64-wide rows keep the full forests and the kernels above.
+// Engine option ensemble_contract chooses how the contracted forests are laid out and walked on those rows:
+//   4 (default), 3 — the dense chunk stream (dense_layout_host; include/fdengine.h documents it), the VD 3 kernel.
+//     A bundle is TPG trees walked by one wave, each a perfect heap of the bundle's depth in a node block of its own
+//     size (4 * 2^d bytes) with a leaf row of 2^d values; node words name the 22 varying slots, and the bin tile holds
+//     only those (11 KiB: no constant bins are written). A chunk is a run of consecutive trees, up to kDenseSMax = 8
+//     bundles that fit the chunk buffer, closed by a 1 KiB chunk table that the DMA puts at a fixed place behind the
+//     buffer: per tree group its bundles (depth, tile row, block offsets), per tree its leaf-index byte and leaf row,
+//     and the next chunk's offset and length. Between two barriers a wave walks every bundle of its group with the
+//     fixed-depth walk_ens_at (walk_dense), the bundles dealt to the groups deepest first so the four end together;
+//     the owner adds the chunk's leaf values in forest order (owner_sum_dense). 4 sorts a chunk's trees by depth
+//     before cutting bundles, 3 keeps consecutive trees.
+//   1 — the padded 1 KiB-block chunks, each wave's trees walked to the deepest of them (walk_pack_var, VD 2);
+//   2 — the same chunks, each tree to its own depth (walk_ens_var, VD 1); 0 — the full forests.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -179,6 +191,19 @@ size_t ens_lds(int nf, bool wide) {
          1024;
 }
 
+// The dense layout (VD 3: contracted forests on compact / split rows, dense_layout_host): the bin tile holds the 22
+// varying slots at their compact indices (11 KiB), each chunk buffer is BUF data bytes + the chunk's 1 KiB table at a
+// fixed place behind them, and a leaf-index tile holds kDenseSMax bundles. Xs | bufA + table | bufB + table | tile0 |
+// tile1 | accA | accB | flags + owner counter, + 1 KiB alignment: 148,608 B wide, 132,224 B compact, 3 KiB under the
+// padded layout's (kDenseSMax 9 would leave 1 KiB, and the two tables take 2).
+constexpr uint32_t kDenseTile = (uint32_t)kDenseSMax * kTile * 8u;
+constexpr uint32_t kDenseTab = 1024, kDenseGroupTab = 64, kDenseTreeTab = 576;  // the chunk table and its parts
+constexpr int kDenseOwnerBias = 0;  // dense_layout_host's owner_bias in the engine's plans
+size_t ens_lds_dense(bool wide) {
+  return (size_t)ens_xs_bytes(kCompactSlots) + 2 * ((size_t)ens_buf(wide) + kDenseTab) + 2 * (size_t)kDenseTile +
+         kTile * 4 + kTile * 8 + 128 + 1024;
+}
+
 struct EnsArgs {
   // Field order: what a wave reads before its first LDS-DMA goes out (rows, pass 0's table image, chunk 0) and the
   // other scalars first, packed into the first few 64-B scalar-cache lines; the per-feature / per-pass tables after
@@ -215,6 +240,12 @@ struct EnsArgs {
   int img_off[kMaxPass + 1];       // pass p's image: bytes [img_off[p], img_off[p + 1]) of img
   int thr_off[kMaxFeatures + 1];  // per-feature table offsets into thr (kernel arguments: scalar loads)
   uint16_t cbin[kMaxFeatures];    // compact mode: the bins of the constant slots (0 or 0.5), per plan
+  // dense kernel: compact slot c's table, elements [cthr[2 c], cthr[2 c + 1]) of thr — the same numbers as thr_off's.
+  // A compiler reason, not an algorithmic one: with thr_off the dense instantiations merge the constant-index reads
+  // into 4- and 8-dword argument loads that the register allocator first spills and then re-loads instead, and the
+  // dead 16-32 B spill slot stays in the frame: a kernel with a private segment (tests/test_kernel_budget.py holds
+  // the hot kernels to none). Read from cthr they compile to 0 B of scratch, at 65 / 54 VGPRs as the other kernels.
+  int cthr[2 * kCompactSlots];
   alignas(4) uint16_t lut[8 * 32];  // compact mode: [kIntSlots][kLutN] bins of the small-integer slots' values 0..31
   BlendConsts blend;
 #ifdef FD_FOREST_PROFILE
@@ -230,12 +261,12 @@ struct EnsArgs {
 // (child) + v_and_or (bin address) + v_and_or (pair address): 4 VALU, 2 LDS reads.
 constexpr uint32_t kLinkMask = 0x3F8u;
 
+// tb[j]: the LDS address of tree j's node block, aligned to the block's 4 * 2^D bytes (the link OR is exact)
 template <int D, int TPG, bool NAN_AWARE>
-__device__ __forceinline__ void walk_ens(uint32_t buf, int t0, uint32_t lane4, uint32_t (&leaf)[TPG]) {
-  uint32_t tb[TPG], node[TPG], kl[TPG], kr[TPG], xw[TPG];
+__device__ __forceinline__ void walk_ens_at(uint32_t (&tb)[TPG], uint32_t lane4, uint32_t (&leaf)[TPG]) {
+  uint32_t node[TPG], kl[TPG], kr[TPG], xw[TPG];
 #pragma unroll
   for (int j = 0; j < TPG; ++j) {
-    tb[j] = buf + (uint32_t)(t0 + j) * 1024u;  // 1 KiB aligned: the link OR is exact
     // in a VGPR: v_and_or_b32 takes one scalar operand on gfx9 (the mask literal), else it splits in two
     asm volatile("" : "+v"(tb[j]));
     node[j] = lds_load<uint32_t>(tb[j] + 4u);
@@ -272,6 +303,15 @@ __device__ __forceinline__ void walk_ens(uint32_t buf, int t0, uint32_t lane4, u
       }
     }
   }
+}
+
+// the padded chunks: tree t0 + j in the 1 KiB block t0 + j of the chunk at buf
+template <int D, int TPG, bool NAN_AWARE>
+__device__ __forceinline__ void walk_ens(uint32_t buf, int t0, uint32_t lane4, uint32_t (&leaf)[TPG]) {
+  uint32_t tb[TPG];
+#pragma unroll
+  for (int j = 0; j < TPG; ++j) tb[j] = buf + (uint32_t)(t0 + j) * 1024u;
+  walk_ens_at<D, TPG, NAN_AWARE>(tb, lane4, leaf);
 }
 
 // Walk this wave's TPG trees of the chunk at `cur` (trees gg*TPG ...) for its 64 transactions; the leaf
@@ -398,6 +438,110 @@ __device__ __forceinline__ unsigned long long walk_pack_var(uint32_t cur, int gg
   return ((unsigned long long)hi << 32) | lo;
 }
 
+// walk_ens_at, the leaf indices packed a byte per tree as walk_pack's
+template <int D, int TPG, bool NAN_AWARE>
+__device__ __forceinline__ unsigned long long walk_pack_at(uint32_t (&tb)[TPG], uint32_t lane4) {
+  uint32_t leaf[TPG];
+  walk_ens_at<D, TPG, NAN_AWARE>(tb, lane4, leaf);
+  uint32_t lo = 0, hi = 0;
+#pragma unroll
+  for (int j = 0; j < TPG; ++j) {
+    if (j < 4) lo |= leaf[j] << (8 * j);
+    else hi |= leaf[j] << (8 * (j - 4));
+  }
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// The dense chunk at `cur`, its table at `tab` (dense_layout_host): this wave walks every bundle the table gives its
+// tree group, deepest first — depth, tile row and the trees' node-block offsets from the bundle's 16-B entry (one
+// broadcast read, depth and row kept scalar; the next entry is read before the walk) — and stores each bundle's leaf bytes to
+// tile[bundle][txn]. counts: word 3 of the table, the groups' bundle counts.
+template <int TPG>
+__device__ __forceinline__ void walk_dense(uint32_t cur, uint32_t tab, uint32_t tw, int gg, int txn, uint32_t lane4,
+                                           bool tile_nan, uint32_t counts) {
+  static_assert(TPG <= 6, "six block offsets per bundle entry");
+  const int nb = (int)((counts >> (8 * gg)) & 0xFFu);
+  const uint32_t ent = tab + kDenseGroupTab + (uint32_t)gg * 128u;
+  u32x4 e = lds_load<u32x4>(ent);
+  for (int s = 0; s < nb; ++s) {
+    // (the offsets stay in VGPRs, where the block addresses are wanted: only the depth and the tile row are scalar)
+    const uint32_t e0 = __builtin_amdgcn_readfirstlane(e.x);
+    const uint32_t off[6] = {e.y & 0xFFFFu, e.y >> 16, e.z & 0xFFFFu, e.z >> 16, e.w & 0xFFFFu, e.w >> 16};
+    e = lds_load<u32x4>(ent + (uint32_t)(s + 1) * 16u);  // (past the group's last entry: still inside the table)
+    uint32_t tb[TPG];
+#pragma unroll
+    for (int j = 0; j < TPG; ++j) tb[j] = cur + off[j];
+    // (packed inside each case: merged after the switch, the TPG leaf indices become one <TPG x i32> value that the
+    // compiler legalises through a stack slot)
+    unsigned long long w;
+#define FD_WALK_DEPTH(K)                                                                                        \
+  case K:                                                                                                       \
+    w = tile_nan ? walk_pack_at<K, TPG, true>(tb, lane4) : walk_pack_at<K, TPG, false>(tb, lane4);              \
+    break;
+    switch (e0 & 0xFFu) {
+      FD_WALK_DEPTH(1)
+      FD_WALK_DEPTH(2)
+      FD_WALK_DEPTH(3)
+      FD_WALK_DEPTH(4)
+      FD_WALK_DEPTH(5)
+      FD_WALK_DEPTH(6)
+      FD_WALK_DEPTH(7)
+      default:
+        w = tile_nan ? walk_pack_at<8, TPG, true>(tb, lane4) : walk_pack_at<8, TPG, false>(tb, lane4);
+        break;
+    }
+#undef FD_WALK_DEPTH
+    lds_store<unsigned long long>(tw + (((e0 >> 8) & 0xFFu) * (uint32_t)kTile + (uint32_t)txn) * 8u,
+                                  w);
+  }
+}
+
+// owner_sum over a dense chunk: the chunk's trees in forest order, tree k's leaf index from the tile byte its table
+// entry names and its value from its leaf row, eight trees at a time — the entries two batches ahead and the indices
+// one batch ahead of the values, so the three dependent reads of a tree overlap its neighbours'. Entries past the
+// chunk's last tree are zero (reads inside the buffer, values not added).
+template <typename LeafT>
+__device__ __forceinline__ void owner_sum_dense(uint32_t buf, uint32_t tab, uint32_t tile, uint32_t acc, int txn) {
+  const int n = (int)(__builtin_amdgcn_readfirstlane(lds_load<uint32_t>(tab)) & 0xFFu);
+  const uint32_t tx = tile + (uint32_t)txn * 8u, ent = tab + kDenseTreeTab;
+  // (entries as two u32x4 per batch, unrolled component reads: no array the compiler could leave on the stack)
+  u32x4 ea = lds_load<u32x4>(ent), eb = lds_load<u32x4>(ent + 16u);
+  u32x4 na = lds_load<u32x4>(ent + 32u), nb = lds_load<u32x4>(ent + 48u);
+  uint32_t i0 = lds_load<uint8_t>(tx + (ea.x & 0xFFFFu)), i1 = lds_load<uint8_t>(tx + (ea.y & 0xFFFFu)),
+           i2 = lds_load<uint8_t>(tx + (ea.z & 0xFFFFu)), i3 = lds_load<uint8_t>(tx + (ea.w & 0xFFFFu)),
+           i4 = lds_load<uint8_t>(tx + (eb.x & 0xFFFFu)), i5 = lds_load<uint8_t>(tx + (eb.y & 0xFFFFu)),
+           i6 = lds_load<uint8_t>(tx + (eb.z & 0xFFFFu)), i7 = lds_load<uint8_t>(tx + (eb.w & 0xFFFFu));
+  LeafT s = lds_load<LeafT>(acc + (uint32_t)txn * (uint32_t)sizeof(LeafT));
+  constexpr uint32_t LS = (uint32_t)sizeof(LeafT);
+  for (int b = 0; b < n; b += 8) {
+    const LeafT v0 = lds_load<LeafT>(buf + (ea.x >> 16) + i0 * LS), v1 = lds_load<LeafT>(buf + (ea.y >> 16) + i1 * LS),
+                v2 = lds_load<LeafT>(buf + (ea.z >> 16) + i2 * LS), v3 = lds_load<LeafT>(buf + (ea.w >> 16) + i3 * LS),
+                v4 = lds_load<LeafT>(buf + (eb.x >> 16) + i4 * LS), v5 = lds_load<LeafT>(buf + (eb.y >> 16) + i5 * LS),
+                v6 = lds_load<LeafT>(buf + (eb.z >> 16) + i6 * LS), v7 = lds_load<LeafT>(buf + (eb.w >> 16) + i7 * LS);
+    ea = na;
+    eb = nb;
+    i0 = lds_load<uint8_t>(tx + (ea.x & 0xFFFFu));
+    i1 = lds_load<uint8_t>(tx + (ea.y & 0xFFFFu));
+    i2 = lds_load<uint8_t>(tx + (ea.z & 0xFFFFu));
+    i3 = lds_load<uint8_t>(tx + (ea.w & 0xFFFFu));
+    i4 = lds_load<uint8_t>(tx + (eb.x & 0xFFFFu));
+    i5 = lds_load<uint8_t>(tx + (eb.y & 0xFFFFu));
+    i6 = lds_load<uint8_t>(tx + (eb.z & 0xFFFFu));
+    i7 = lds_load<uint8_t>(tx + (eb.w & 0xFFFFu));
+    na = lds_load<u32x4>(ent + (uint32_t)(b + 16) * 4u);
+    nb = lds_load<u32x4>(ent + (uint32_t)(b + 16) * 4u + 16u);
+    s = b + 0 < n ? s + v0 : s;
+    s = b + 1 < n ? s + v1 : s;
+    s = b + 2 < n ? s + v2 : s;
+    s = b + 3 < n ? s + v3 : s;
+    s = b + 4 < n ? s + v4 : s;
+    s = b + 5 < n ? s + v5 : s;
+    s = b + 6 < n ? s + v6 : s;
+    s = b + 7 < n ? s + v7 : s;
+  }
+  lds_store<LeafT>(acc + (uint32_t)txn * (uint32_t)sizeof(LeafT), s);
+}
+
 // One transaction's share of a finished chunk: its CH leaf values (indices from the tile, values from the
 // chunk's leaf block in LDS) added in tree order to the forest's running sum — the reference's sequential
 // f32 margin / f64 path-length sum, bit for bit.
@@ -428,6 +572,25 @@ __device__ __forceinline__ void stage_pieces(const char* __restrict__ src, uint3
   for (int p = part; p < pieces; p += nparts) {
     const char* g = src + (p << 10) + lane * 16;
     const uint32_t m0 = __builtin_amdgcn_readfirstlane(dst + ((uint32_t)p << 10));
+    asm volatile(
+        "s_mov_b32 m0, %0\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, off"
+        :
+        : "s"(m0), "v"(g)
+        : "memory", "m0");
+  }
+}
+
+// A dense chunk's image (bytes: its data pieces, then its 1 KiB table) into the buffer at dst, the table to its fixed
+// place tab behind the buffer's data bytes; as stage_pieces
+__device__ __forceinline__ void stage_dense(const char* __restrict__ src, uint32_t dst, uint32_t tab, int bytes,
+                                            int nparts, int part) {
+  const int lane = threadIdx.x & 63;
+  const int pieces = bytes >> 10;
+  for (int p = part; p < pieces; p += nparts) {
+    const char* g = src + (p << 10) + lane * 16;
+    const uint32_t m0 = __builtin_amdgcn_readfirstlane(p + 1 < pieces ? dst + ((uint32_t)p << 10) : tab);
     asm volatile(
         "s_mov_b32 m0, %0\n\t"
         "s_nop 0\n\t"
@@ -616,7 +779,9 @@ __device__ __forceinline__ void load_split(const uint4* __restrict__ ra, const u
   }
 }
 
-template <int Q, int L, bool LUT>
+// CS: the bin tile holds the varying slots only, slot Q + 4 i at its compact index (the dense layout's node words name
+// it), else every feature at its own index
+template <int Q, int L, bool LUT, bool CS = false>
 __device__ __forceinline__ void bin_compact_pass(const EnsArgs& a, const float (&v)[16], uint16_t* Xs,
                                                  int txn, int f0, int f1, bool glob, uint32_t tl, int o0,
                                                  int& anynan, uint32_t lut) {
@@ -638,14 +803,17 @@ __device__ __forceinline__ void bin_compact_pass(const EnsArgs& a, const float (
       bin = lds_load<uint16_t>(lut + (uint32_t)(ks * kLutN + (int)x) * 2u);
     } else {  // #{t <= x} over the feature's merged table in global memory: binary lifting with a fixed trip count
       // (tables hold < 2^16 thresholds), straight-line code, so this loop over i stays unrolled and v[] in registers
-      const int o = a.thr_off[f], cnt = a.thr_off[f + 1] - o;
+      // (CS: the slot's bounds from cthr as below — EnsArgs::cthr says why)
+      const int o = CS ? a.cthr[2 * (Q + 4 * i)] : a.thr_off[f];
+      const int cnt = (CS ? a.cthr[2 * (Q + 4 * i) + 1] : a.thr_off[f + 1]) - o;
       int pos = 0;
 #pragma unroll
       for (int st = 1 << 15; st > 0; st >>= 1)
         if (pos + st <= cnt && a.thr[o + pos + st - 1] <= x) pos += st;
       bin = (uint16_t)pos;
     }
-    Xs[(f >> 1) * 512 + txn * 2 + (f & 1)] = bin;
+    const int at = CS ? Q + 4 * i : f;
+    Xs[(at >> 1) * 512 + txn * 2 + (at & 1)] = bin;
   }
   // the others: binary lifting in lockstep groups of L
 #pragma unroll
@@ -660,8 +828,8 @@ __device__ __forceinline__ void bin_compact_pass(const EnsArgs& a, const float (
       const int f = kCompactSlot[Q + 4 * i];
       act[k] = g0 + k < NS && f >= f0 && f < f1 && f < a.nf;
       vv[k] = act[k] ? v[i] : 0.f;  // v[i]: compact slot Q + 4 i of the row
-      o[k] = act[k] ? a.thr_off[f] : o0;
-      cnt[k] = act[k] ? a.thr_off[f + 1] - o[k] : 0;
+      o[k] = act[k] ? (CS ? a.cthr[2 * (Q + 4 * i)] : a.thr_off[f]) : o0;
+      cnt[k] = act[k] ? (CS ? a.cthr[2 * (Q + 4 * i) + 1] : a.thr_off[f + 1]) - o[k] : 0;
       pos[k] = 0;
       steps = max(steps, lift_steps(cnt[k]));
     }
@@ -673,7 +841,8 @@ __device__ __forceinline__ void bin_compact_pass(const EnsArgs& a, const float (
       if (act[k]) {
         const bool nan = vv[k] != vv[k];
         anynan |= nan ? 1 : 0;
-        Xs[(f >> 1) * 512 + txn * 2 + (f & 1)] = nan ? (uint16_t)0xFFFFu : (uint16_t)pos[k];
+        const int at = CS ? Q + 4 * i : f;
+        Xs[(at >> 1) * 512 + txn * 2 + (at & 1)] = nan ? (uint16_t)0xFFFFu : (uint16_t)pos[k];
       }
     }
   }
@@ -693,9 +862,12 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
   const int gg = __builtin_amdgcn_readfirstlane(wave >> 2);  // wave-uniform: scalar addressing
   const int txn = ((wave & 3) << 6) + lane;
   const uint32_t lane4 = s0 + (uint32_t)txn * 4u;
-  const uint32_t bufA = s0 + ens_xs_bytes(a.nf), bufB = bufA + kEnsBuf;
-  const uint32_t tile0 = bufB + kEnsBuf, tile1 = tile0 + kEnsTile;
-  const uint32_t accA = tile1 + kEnsTile, accB = accA + kTile * 4;
+  // VD 3 (dense chunks): the 22-slot bin tile, a chunk table behind each buffer, tiles of kDenseSMax bundles
+  constexpr bool DENSE = VD == 3;
+  constexpr uint32_t kBufStep = kEnsBuf + (DENSE ? kDenseTab : 0u), kTileBytes = DENSE ? kDenseTile : kEnsTile;
+  const uint32_t bufA = s0 + (DENSE ? ens_xs_bytes(kCompactSlots) : ens_xs_bytes(a.nf)), bufB = bufA + kBufStep;
+  const uint32_t tile0 = bufB + kBufStep, tile1 = tile0 + kTileBytes;
+  const uint32_t accA = tile1 + kTileBytes, accB = accA + kTile * 4;
   const uint32_t flags = accB + kTile * 8, owner_cnt = flags + 64;
   const int64_t row = (int64_t)blockIdx.x * kTile + txn;
   const bool valid = row < a.n;
@@ -741,20 +913,20 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
       const uint4* ra = reinterpret_cast<const uint4*>(a.X) + 2 * row;
       const uint4* rb = reinterpret_cast<const uint4*>(a.X) + 2 * (a.n + row);
       switch (q) {  // wave-uniform
-        case 0: load_split<0>(ra, rb, v); bin_compact_constants<0>(a, Xs, txn); break;
-        case 1: load_split<1>(ra, rb, v); bin_compact_constants<1>(a, Xs, txn); break;
-        case 2: load_split<2>(ra, rb, v); bin_compact_constants<2>(a, Xs, txn); break;
-        default: load_split<3>(ra, rb, v); bin_compact_constants<3>(a, Xs, txn); break;
+        case 0: load_split<0>(ra, rb, v); if (!DENSE) bin_compact_constants<0>(a, Xs, txn); break;
+        case 1: load_split<1>(ra, rb, v); if (!DENSE) bin_compact_constants<1>(a, Xs, txn); break;
+        case 2: load_split<2>(ra, rb, v); if (!DENSE) bin_compact_constants<2>(a, Xs, txn); break;
+        default: load_split<3>(ra, rb, v); if (!DENSE) bin_compact_constants<3>(a, Xs, txn); break;
       }
     } else if (valid && a.compact) {
       const float* xr = a.X + row * (int64_t)kCompactWidth;
       switch (q) {  // wave-uniform
-        case 0: load_compact<0>(xr, v); bin_compact_constants<0>(a, Xs, txn); break;
-        case 1: load_compact<1>(xr, v); bin_compact_constants<1>(a, Xs, txn); break;
-        case 2: load_compact<2>(xr, v); bin_compact_constants<2>(a, Xs, txn); break;
-        default: load_compact<3>(xr, v); bin_compact_constants<3>(a, Xs, txn); break;
+        case 0: load_compact<0>(xr, v); if (!DENSE) bin_compact_constants<0>(a, Xs, txn); break;
+        case 1: load_compact<1>(xr, v); if (!DENSE) bin_compact_constants<1>(a, Xs, txn); break;
+        case 2: load_compact<2>(xr, v); if (!DENSE) bin_compact_constants<2>(a, Xs, txn); break;
+        default: load_compact<3>(xr, v); if (!DENSE) bin_compact_constants<3>(a, Xs, txn); break;
       }
-    } else if (valid) {
+    } else if (!DENSE && valid) {  // (the dense kernel's rows are compact or split: its tile has no 64 slots)
       const float* xr = a.X + row * (int64_t)a.ld;
       const int ncopy = a.ld < a.nf ? a.ld : a.nf;
       if (a.vec4 && fq + 16 <= ncopy) {
@@ -776,7 +948,13 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
     // search in global memory instead (engine option ensemble_bin_global): nothing staged, so chunk 0's DMA goes out
     if (a.n_pass > 0 && !(a.pass_global & 1ull))
       stage_pieces(a.img + a.img_off[0], bufA, a.img_off[1] - a.img_off[0], kEnsWG / 64, wave);
-    if (early0) stage_chunk_asm(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, nA > 0 ? a.stride[0] : a.stride[1], kEnsWG / 64);
+    if (early0) {
+      if (DENSE)
+        stage_dense(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, bufA + kEnsBuf, nA > 0 ? a.stride[0] : a.stride[1],
+                    kEnsWG / 64, wave);
+      else
+        stage_chunk_asm(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, nA > 0 ? a.stride[0] : a.stride[1], kEnsWG / 64);
+    }
 #ifdef FD_FOREST_PROFILE
     pr_st[0] = __builtin_amdgcn_s_memtime();
 #endif
@@ -805,19 +983,19 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
 #endif
       if (LUT && valid && a.compact) {
         switch (q) {
-          case 0: bin_compact_pass<0, kLock, true>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          case 1: bin_compact_pass<1, kLock, true>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          case 2: bin_compact_pass<2, kLock, true>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          default: bin_compact_pass<3, kLock, true>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          case 0: bin_compact_pass<0, kLock, true, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          case 1: bin_compact_pass<1, kLock, true, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          case 2: bin_compact_pass<2, kLock, true, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          default: bin_compact_pass<3, kLock, true, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
         }
       } else if (valid && a.compact) {
         switch (q) {
-          case 0: bin_compact_pass<0, kLock, false>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          case 1: bin_compact_pass<1, kLock, false>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          case 2: bin_compact_pass<2, kLock, false>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          default: bin_compact_pass<3, kLock, false>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          case 0: bin_compact_pass<0, kLock, false, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          case 1: bin_compact_pass<1, kLock, false, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          case 2: bin_compact_pass<2, kLock, false, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          default: bin_compact_pass<3, kLock, false, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
         }
-      } else if (valid) {
+      } else if (!DENSE && valid) {
 #pragma unroll
         for (int kk = 0; kk < 16; kk += kLock) {
           const int fb = fq + kk;
@@ -885,8 +1063,13 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
 #endif
     }
   }
-  if (G > 0 && !early0)  // chunk 0 (the tables are dead): forest A's first, or B's when A is absent
-    stage_pieces(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, nA > 0 ? a.stride[0] : a.stride[1], kEnsWG / 64, wave);
+  if (G > 0 && !early0) {  // chunk 0 (the tables are dead): forest A's first, or B's when A is absent
+    if (DENSE)  // (stride: the first chunk's length)
+      stage_dense(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, bufA + kEnsBuf, nA > 0 ? a.stride[0] : a.stride[1],
+                  kEnsWG / 64, wave);
+    else
+      stage_pieces(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, nA > 0 ? a.stride[0] : a.stride[1], kEnsWG / 64, wave);
+  }
   if (gg == 0) {
     lds_store<float>(accA + txn * 4, a.base_margin);
     lds_store<double>(accB + txn * 8, 0.0);
@@ -903,11 +1086,24 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
   for (int g = 0; g < G; ++g) {
     FD_ESTAMP(q0);
     const bool owner = gg == (a.owner_fixed ? 0 : ((g - 1) & 3));
+    const uint32_t cur = (g & 1) ? bufB : bufA, tw = (g & 1) ? tile1 : tile0;
+    // dense: words 0..3 of this chunk's table — its tree and bundle counts, the next chunk's offset and length in
+    // KiB, the groups' bundle counts — in SGPRs
+    uint32_t th1 = 0, th2 = 0, th3 = 0;
+    if (DENSE) {
+      const u32x4 h = lds_load<u32x4>(cur + kEnsBuf);
+      th1 = __builtin_amdgcn_readfirstlane(h.y);
+      th2 = __builtin_amdgcn_readfirstlane(h.z);
+      th3 = __builtin_amdgcn_readfirstlane(h.w);
+    }
     if (owner) {
       if (g > 0) {
         const int c = g - 1;
         const uint32_t bp = (c & 1) ? bufB : bufA, tp = (c & 1) ? tile1 : tile0;
-        if (c < nA) owner_sum<D, TPGA, kCHA, float>(bp, tp, accA, txn, NL);
+        if (DENSE) {
+          if (c < nA) owner_sum_dense<float>(bp, bp + kEnsBuf, tp, accA, txn);
+          else owner_sum_dense<double>(bp, bp + kEnsBuf, tp, accB, txn);
+        } else if (c < nA) owner_sum<D, TPGA, kCHA, float>(bp, tp, accA, txn, NL);
         else owner_sum<D, TPGB, kCHB, double>(bp, tp, accB, txn, NL);
         // the leaf reads of all four owner waves are complete before any of them overwrites the buffer
         if (lane == 0)
@@ -919,18 +1115,28 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
       }
       if (g + 1 < G) {
         const int h = g + 1, fb = h >= nA ? 1 : 0;
-        stage_pieces(a.nodes[fb] + (size_t)(fb ? h - nA : h) * a.stride[fb], (g & 1) ? bufA : bufB, a.stride[fb], 4,
-                  wave & 3);
+        const uint32_t nb = (g & 1) ? bufA : bufB;
+        if (DENSE) {  // forest B's first chunk by the arguments, any other by this chunk's table
+          if (h == nA) stage_dense(a.nodes[1], nb, nb + kEnsBuf, a.stride[1], 4, wave & 3);
+          else stage_dense(a.nodes[fb] + ((size_t)th1 << 10), nb, nb + kEnsBuf, (int)(th2 << 10), 4, wave & 3);
+        } else {
+          stage_pieces(a.nodes[fb] + (size_t)(fb ? h - nA : h) * a.stride[fb], nb, a.stride[fb], 4, wave & 3);
+        }
       }
     }
-    const uint32_t cur = (g & 1) ? bufB : bufA, tw = (g & 1) ? tile1 : tile0;
     FD_ESTAMP(q1);
-    unsigned long long w;
-    if (VD)
-      w = g < nA ? walk_pack_var<VD, TPGA>(cur, gg, lane4, tile_nan) : walk_pack_var<VD, TPGB>(cur, gg, lane4, tile_nan);
-    else
-      w = g < nA ? walk_pack<D, TPGA>(cur, gg, lane4, tile_nan) : walk_pack<D, TPGB>(cur, gg, lane4, tile_nan);
-    lds_store<unsigned long long>(tw + (uint32_t)(gg * kTile + txn) * 8u, w);
+    if (DENSE) {
+      if (g < nA) walk_dense<TPGA>(cur, cur + kEnsBuf, tw, gg, txn, lane4, tile_nan, th3);
+      else walk_dense<TPGB>(cur, cur + kEnsBuf, tw, gg, txn, lane4, tile_nan, th3);
+    } else {
+      unsigned long long w;
+      if (VD)
+        w = g < nA ? walk_pack_var<VD, TPGA>(cur, gg, lane4, tile_nan)
+                   : walk_pack_var<VD, TPGB>(cur, gg, lane4, tile_nan);
+      else
+        w = g < nA ? walk_pack<D, TPGA>(cur, gg, lane4, tile_nan) : walk_pack<D, TPGB>(cur, gg, lane4, tile_nan);
+      lds_store<unsigned long long>(tw + (uint32_t)(gg * kTile + txn) * 8u, w);
+    }
     FD_ESTAMP(q2);
     if (owner) dma_wait();
 #ifdef FD_FOREST_PROFILE
@@ -948,7 +1154,10 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
   if (G > 0 && gg == (a.owner_fixed ? 0 : ((G - 1) & 3))) {
     const int c = G - 1;
     const uint32_t bp = (c & 1) ? bufB : bufA, tp = (c & 1) ? tile1 : tile0;
-    if (c < nA) owner_sum<D, TPGA, kCHA, float>(bp, tp, accA, txn, NL);
+    if (DENSE) {
+      if (c < nA) owner_sum_dense<float>(bp, bp + kEnsBuf, tp, accA, txn);
+      else owner_sum_dense<double>(bp, bp + kEnsBuf, tp, accB, txn);
+    } else if (c < nA) owner_sum<D, TPGA, kCHA, float>(bp, tp, accA, txn, NL);
     else owner_sum<D, TPGB, kCHB, double>(bp, tp, accB, txn, NL);
   }
   __syncthreads();
@@ -1051,6 +1260,10 @@ const void* pick_ensemble_var(int out, bool wide, int vd) {
     if (wide) return out == 1 ? (const void*)ensemble_kernel<8, 1, true, true, 2> : (const void*)ensemble_kernel<8, 0, true, true, 2>;
     return out == 1 ? (const void*)ensemble_kernel<8, 1, false, true, 2> : (const void*)ensemble_kernel<8, 0, false, true, 2>;
   }
+  if (vd == 3) {
+    if (wide) return out == 1 ? (const void*)ensemble_kernel<8, 1, true, true, 3> : (const void*)ensemble_kernel<8, 0, true, true, 3>;
+    return out == 1 ? (const void*)ensemble_kernel<8, 1, false, true, 3> : (const void*)ensemble_kernel<8, 0, false, true, 3>;
+  }
   if (wide) return out == 1 ? (const void*)ensemble_kernel<8, 1, true, true, 1> : (const void*)ensemble_kernel<8, 0, true, true, 1>;
   return out == 1 ? (const void*)ensemble_kernel<8, 1, false, true, 1> : (const void*)ensemble_kernel<8, 0, false, true, 1>;
 }
@@ -1070,7 +1283,9 @@ fd_tree_arrays arrays_of(const PackedForest& f) {
 
 // Binning passes over the tables (thr, off): consecutive features whose padded tables fit the staging area (bufA +
 // bufB + the tiles), a larger table alone, searched in global memory; each staged pass's image (element g of the
-// pass at word thr_pad(g), 1 KiB pieces) appended to img
+// pass at word thr_pad(g), 1 KiB pieces) appended to img. The staging area is sized by the padded layout for the dense
+// kernel too: a plan's passes serve both (64-wide rows keep the padded kernels), and the dense kernel's area behind its
+// 11 KiB tile is the larger (133,120 B against 114,688 B wide), so a pass that fits here fits there.
 void plan_passes(const std::vector<float>& thr, const std::vector<int32_t>& off, int nf, bool wide, EnsPassSet& ps,
                  std::vector<float>& img) {
   const size_t stage_floats = (2 * (size_t)ens_buf(wide) + 2 * (size_t)kEnsTile) / 4;
@@ -1198,10 +1413,23 @@ bool build_plan(Engine& e, EnsemblePlan& P, int sa, int sb, bool wide, int contr
   P.contracted = false;
   P.nodes_pruned = 0;
   P.steps_full = P.steps_c = 0;
+  P.dense_len0[0] = P.dense_len0[1] = P.dense_chunks[0] = P.dense_chunks[1] = 0;
   for (int k = 0; k < 2 && contract; ++k) {
     if (!F[k]) continue;
     const bool xgb = F[k]->params.kind == FD_FOREST_XGB_BINARY_LOGISTIC;
     const ContractedForest c = contract_forest_host(F[k]->params, arrays_of(*F[k]));
+    if (contract >= 3) {  // the dense chunk stream (dense_layout_host), walked by the VD 3 kernel
+      FD_REQUIRE(ens_lds_dense(wide) <= ens_lds(kMaxFeatures, wide), FD_ERR_UNSUPPORTED,
+                 "dense layout: more LDS than the padded layout");
+      const DenseLayout L = dense_layout_host(c, xgb, merged, wide, contract, kDenseOwnerBias);
+      P.nodes_c[k].ensure(L.blob.size());
+      FD_HIP(hipMemcpy(P.nodes_c[k].ptr, L.blob.data(), L.blob.size(), hipMemcpyHostToDevice));
+      P.dense_len0[k] = L.chunk_len.empty() ? 0 : L.chunk_len[0];
+      P.dense_chunks[k] = (int)L.chunk_len.size();
+      P.steps_c += L.steps;
+      P.nodes_pruned += c.pruned;
+      continue;
+    }
     const int T = hp[k].n_trees, nc = P.n_chunks[k], ch = CH[k], tpg = ch / 4;
     const size_t nb = (size_t)nc * ch;
     std::vector<int> dw(nb, 1);
@@ -1314,6 +1542,189 @@ bool want_wide(const Engine& e) { return e.ens_chunks == 1 || (e.ens_chunks == 0
 
 }  // namespace
 
+// The dense chunk stream of one contracted forest (include/fdengine.h fd_dense_layout_host: the layout, the chunk
+// table and the node word): build_plan's chunks under ensemble_contract 3 / 4 and the host export, one function.
+DenseLayout dense_layout_host(const ContractedForest& c, bool xgb, const std::vector<std::vector<float>>& tables,
+                              bool wide, int mode, int owner_bias) {
+  FD_REQUIRE(mode == 3 || mode == 4, FD_ERR_INVALID_ARG, "dense layout: mode 3 or 4");
+  FD_REQUIRE(owner_bias >= 0 && owner_bias <= 64, FD_ERR_INVALID_ARG, "dense layout: owner_bias in [0, 64]");
+  DenseLayout L;
+  const int T = (int)c.off.size() - 1;
+  const int tpg = (xgb ? (wide ? EnsCfg<true>::CHA : EnsCfg<false>::CHA) : (wide ? EnsCfg<true>::CHB : EnsCfg<false>::CHB)) / 4;
+  const size_t lsz = xgb ? 4 : 8;
+  L.tpg = tpg;
+  L.buf = ens_buf(wide);
+  L.tree.assign((size_t)T, fd_dense_tree{});
+  for (int i = 0; i < T; ++i)
+    FD_REQUIRE(c.depth[i] >= 1 && c.depth[i] <= 8, FD_ERR_UNSUPPORTED, "dense layout: a tree deeper than 8 levels");
+  struct Bundle {
+    std::vector<int> trees;  // forest indices, in place order
+    int depth = 1;
+  };
+  // trees [i0, i0 + n) as bundles, and the data bytes they take
+  auto bundle_up = [&](int i0, int n, std::vector<Bundle>& B) {
+    std::vector<int> order(n);
+    for (int k = 0; k < n; ++k) order[k] = i0 + k;
+    if (mode == 4)
+      std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return c.depth[x] > c.depth[y]; });
+    B.clear();
+    size_t bytes = 0;
+    // a partial bundle (the forest's last chunk): in mode 3 the forest's last trees; in mode 4 at the place in the
+    // sorted order where the sum of the walked depths is least (the last such place) — some place is optimal for these
+    // bundle sizes, so mode 4 never walks more levels than mode 3
+    const int nbund = (n + tpg - 1) / tpg, part = n % tpg;
+    int where = nbund - 1;
+    if (mode == 4 && part) {
+      long long best = -1;
+      for (int w = 0; w < nbund; ++w) {
+        long long cost = 0;
+        for (int q = 0, k = 0; q < nbund; ++q) {
+          const int sz = q == w ? part : tpg;
+          cost += (long long)sz * c.depth[order[k]];  // sorted: the bundle's first tree is its deepest
+          k += sz;
+        }
+        if (best < 0 || cost <= best) best = cost, where = w;
+      }
+    }
+    for (int q = 0, k = 0; q < nbund; ++q) {
+      const int sz = (part && q == where) ? part : tpg;
+      Bundle b;
+      b.trees.assign(order.begin() + k, order.begin() + k + sz);
+      k += sz;
+      for (int t : b.trees) b.depth = std::max(b.depth, (int)c.depth[t]);
+      bytes += b.trees.size() * ((4 + lsz) << b.depth);
+      B.push_back(std::move(b));
+    }
+    return bytes;
+  };
+  std::vector<Bundle> B, cand;
+  std::vector<int32_t> cur(2 * 256);
+  int i0 = 0;
+  while (i0 < T) {
+    int n = 0;
+    for (int m = tpg;; m += tpg) {  // grow by a bundle's worth of trees while the caps hold
+      const int me = std::min(m, T - i0);
+      const size_t bytes = bundle_up(i0, me, cand);
+      if ((int)cand.size() > kDenseSMax || bytes > L.buf) break;
+      n = me;
+      B = cand;
+      if (i0 + m >= T) break;
+    }
+    FD_REQUIRE(n > 0, FD_ERR_UNSUPPORTED, "dense layout: one bundle exceeds the chunk buffer");
+    const int nb = (int)B.size(), ci = (int)L.chunk_off.size();
+    // blocks: the node blocks by size (every block aligned to its own size), then the leaf rows in forest order
+    std::vector<int> by_size;
+    std::vector<int> bundle_of(n), place_of(n);
+    for (int b = 0; b < nb; ++b)
+      for (size_t j = 0; j < B[b].trees.size(); ++j) {
+        bundle_of[B[b].trees[j] - i0] = b;
+        place_of[B[b].trees[j] - i0] = (int)j;
+      }
+    for (int k = 0; k < n; ++k) by_size.push_back(k);
+    std::stable_sort(by_size.begin(), by_size.end(),
+                     [&](int x, int y) { return B[bundle_of[x]].depth > B[bundle_of[y]].depth; });
+    size_t at = 0;
+    for (int k : by_size) {
+      L.tree[i0 + k].node_offset = (int32_t)at;
+      at += (size_t)4 << B[bundle_of[k]].depth;
+    }
+    for (int k = 0; k < n; ++k) {
+      L.tree[i0 + k].leaf_offset = (int32_t)at;
+      at += lsz << B[bundle_of[k]].depth;
+    }
+    FD_REQUIRE(at <= L.buf, FD_ERR_UNSUPPORTED, "dense layout: chunk data exceed the buffer");
+    const size_t data = (at + 1023) / 1024 * 1024, base = L.blob.size();
+    L.blob.resize(base + data + 1024, 0);
+    L.chunk_off.push_back((int64_t)base);
+    L.chunk_len.push_back((int32_t)(data + 1024));
+    char* chunk = L.blob.data() + base;
+    // deal the bundles to the tree groups: deepest first, each to the least loaded group
+    std::vector<int> deal(nb);
+    for (int b = 0; b < nb; ++b) deal[b] = b;
+    std::stable_sort(deal.begin(), deal.end(), [&](int x, int y) { return B[x].depth > B[y].depth; });
+    long long load[4] = {(long long)owner_bias * n, 0, 0, 0};  // sixteenths of a level
+    std::vector<int> group_of(nb);
+    std::vector<std::vector<int>> of_group(4);
+    for (int b : deal) {
+      int g = 0;
+      for (int q = 1; q < 4; ++q)
+        if (load[q] < load[g]) g = q;
+      load[g] += 16ll * B[b].depth;
+      group_of[b] = g;
+      of_group[g].push_back(b);
+    }
+    // the trees
+    for (int k = 0; k < n; ++k) {
+      const int i = i0 + k, dw = B[bundle_of[k]].depth, nl = 1 << dw;
+      fd_dense_tree& t = L.tree[i];
+      t.chunk = ci;
+      t.bundle = bundle_of[k];
+      t.group = group_of[bundle_of[k]];
+      t.depth = dw;
+      L.steps += dw;
+      uint32_t* dst = reinterpret_cast<uint32_t*>(chunk + t.node_offset);
+      const int64_t a = c.off[i];
+      cur[1] = 0;
+      for (int s = 1; s < nl; ++s) {
+        const int32_t o = cur[s];
+        const uint32_t link = s < (nl >> 1) ? (uint32_t)s : (uint32_t)(s - (nl >> 1));
+        if (c.left[a + o] < 0) {  // a leaf above depth dw: pad node, both ways reach it
+          dst[s] = link << 3;
+          cur[2 * s] = cur[2 * s + 1] = o;
+          continue;
+        }
+        const int f = c.feature[a + o];
+        FD_REQUIRE(f >= 0 && f < (int)tables.size() && compact_src(f) >= 0, FD_ERR_UNSUPPORTED,
+                   "dense layout: a split on a constant slot");
+        const uint32_t cs = (uint32_t)compact_src(f);
+        const float thr = xgb ? (float)c.threshold[a + o] : sklearn_threshold_to_lt(c.threshold[a + o]);
+        const std::vector<float>& tb = tables[(size_t)f];
+        const uint32_t jm = (uint32_t)(std::lower_bound(tb.begin(), tb.end(), thr) - tb.begin());
+        // (the root of a tree that resolved to one leaf tests slot 0 against 0, which no table need hold: both ways
+        // reach the same value)
+        FD_REQUIRE(jm <= 0xFFFFu, FD_ERR_UNSUPPORTED, "dense layout: threshold index beyond 16 bits");
+        dst[s] = (jm << 16) | ((cs >> 1) << 10) | (link << 3) | ((cs & 1u) << 1) | (c.dleft[a + o] ? 1u : 0u);
+        cur[2 * s] = c.left[a + o];
+        cur[2 * s + 1] = c.right[a + o];
+      }
+      char* leaves = chunk + t.leaf_offset;
+      for (int s = 0; s < nl; ++s) {
+        const double v = c.leaf[a + cur[nl + s]];
+        if (xgb) {
+          const float vf = (float)v;
+          std::memcpy(leaves + (size_t)s * 4, &vf, 4);
+        } else {
+          std::memcpy(leaves + (size_t)s * 8, &v, 8);
+        }
+      }
+    }
+    // the chunk table
+    uint32_t* tab = reinterpret_cast<uint32_t*>(chunk + data);
+    tab[0] = (uint32_t)n | ((uint32_t)nb << 8);
+    if (ci > 0) {  // the previous chunk's table names this one
+      uint32_t* prev = reinterpret_cast<uint32_t*>(L.blob.data() + L.chunk_off[ci - 1] + L.chunk_len[ci - 1] - 1024);
+      prev[1] = (uint32_t)(base >> 10);
+      prev[2] = (uint32_t)((data + 1024) >> 10);
+    }
+    for (int g = 0; g < 4; ++g) {
+      tab[3] |= (uint32_t)of_group[g].size() << (8 * g);
+      for (size_t s = 0; s < of_group[g].size(); ++s) {
+        const int b = of_group[g][s];
+        uint32_t* e = tab + (64 + 128 * g + 16 * s) / 4;
+        e[0] = (uint32_t)B[b].depth | ((uint32_t)b << 8) | ((uint32_t)g << 16);
+        for (int j = 0; j < 6; ++j) {
+          const int t = B[b].trees[(size_t)j < B[b].trees.size() ? j : 0];
+          e[1 + j / 2] |= (uint32_t)L.tree[t].node_offset << (16 * (j & 1));
+        }
+      }
+    }
+    for (int k = 0; k < n; ++k)
+      tab[576 / 4 + k] = (uint32_t)(2048 * bundle_of[k] + place_of[k]) | ((uint32_t)L.tree[i0 + k].leaf_offset << 16);
+    i0 += n;
+  }
+  return L;
+}
+
 #ifdef FD_FOREST_PROFILE
 // n words from the start of the buffers: slot k's profile at word k * 256 * 16 * 16; *next_slot (if given) = the slot
 // the next launch writes (so the most recent launch wrote (next_slot + kEprofSlots - 1) % kEprofSlots)
@@ -1377,6 +1788,11 @@ void plan_args(const EnsemblePlan& P, const float* dX, int64_t n, int32_t ld, bo
   for (int f = 0; f <= P.nf; ++f) a.thr_off[f] = P.h_thr_off[f];
   a.owner_fixed = owner_fixed ? 1 : 0;
   for (int f = 0; f < kMaxFeatures; ++f) a.cbin[f] = f < (int)P.h_cbin.size() ? P.h_cbin[f] : 0;
+  for (int c = 0; c < kCompactSlots; ++c) {
+    const int f = kCompactSlot[c];
+    a.cthr[2 * c] = f < P.nf ? P.h_thr_off[f] : 0;
+    a.cthr[2 * c + 1] = f < P.nf ? P.h_thr_off[f + 1] : 0;
+  }
   for (size_t k = 0; k < P.h_lut.size() && k < sizeof(a.lut) / sizeof(a.lut[0]); ++k) a.lut[k] = P.h_lut[k];
   a.vec4 = (ld % 4 == 0 && (reinterpret_cast<uintptr_t>(dX) & 15u) == 0) ? 1 : 0;
   const EnsPassSet& ps = P.passes;  // plan_passes
@@ -1401,7 +1817,7 @@ void plan_args(const EnsemblePlan& P, const float* dX, int64_t n, int32_t ld, bo
 bool run_plan(Engine& e, const EnsemblePlan& P, EnsArgs& a, int out, int timing_kind, int vd = 0) {
   const void* fn = vd && out != 2 ? pick_ensemble_var(out, P.wide, vd) : pick_ensemble(out, P.wide, P.D);
   if (!fn) return false;
-  const size_t lds = ens_lds(P.nf, P.wide);
+  const size_t lds = vd == 3 ? ens_lds_dense(P.wide) : ens_lds(P.nf, P.wide);
   FD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int64_t blocks = (a.n + kTile - 1) / kTile;
   Engine::Timed* ev = e.timing ? e.next_event_pair(timing_kind) : nullptr;
@@ -1456,14 +1872,21 @@ bool launch_ensemble(Engine& e, const fd_blend_params& p, const int32_t* slots, 
   FD_REQUIRE(out == 1 || dfp != nullptr, FD_ERR_INVALID_ARG, "null output");
   // compact / split rows carry the constant slots' values by construction: the contracted chunks and the
   // variable-depth walk, when the contraction shortened any tree; 64-wide rows keep nodes[] and the fixed-depth kernels
-  const int vd = (compact && e.ens.contracted) ? (e.ens.contract == 1 ? 2 : 1) : 0;  // walk_pack_var's VD
+  // (the kernel's VD: 1 per tree, 2 per wave, 3 the dense chunk stream of ensemble_contract 3 / 4)
+  const int vd = (compact && e.ens.contracted) ? (e.ens.contract >= 3 ? 3 : e.ens.contract == 1 ? 2 : 1) : 0;
   if (vd) {
     for (int k = 0; k < 2; ++k) a.nodes[k] = e.ens.nodes_c[k].as<const char>();
     a.ldepth = e.ens.D;
   }
+  if (vd == 3)
+    for (int k = 0; k < 2; ++k) {
+      a.n_chunks[k] = e.ens.dense_chunks[k];
+      a.stride[k] = e.ens.dense_len0[k];  // the first chunk's length: the others' come with the tables
+    }
   if (!run_plan(e, e.ens, a, out, FD_TIMING_ENSEMBLE, vd)) return false;
   if (vd) ++e.ens_contract_total;
   e.ens_steps_last = vd ? e.ens.steps_c : e.ens.steps_full;
+  e.ens_dense_chunks_last = vd == 3 ? e.ens.dense_chunks[0] + e.ens.dense_chunks[1] : 0;
   return true;
 }
 

@@ -248,6 +248,9 @@ struct EnsemblePlan {
   bool contracted = false;
   long long nodes_pruned = 0;           // splits of the loaded forests that the contracted ones no longer hold
   long long steps_full = 0, steps_c = 0;  // node steps per transaction: n_trees x D over both forests / sum of d_t
+  // contract 3 / 4: nodes_c[] hold the dense chunk stream (ensemble.hip dense_layout_host) — chunks of their own
+  // lengths, each closed by its 1 KiB chunk table; the first chunk's length and the chunk count per forest
+  int dense_len0[2] = {0, 0}, dense_chunks[2] = {0, 0};
 };
 
 // A forest with every split on a constant slot of the compact scoring vector (compact_src(f) < 0: the value 0.5 or 0)
@@ -272,6 +275,23 @@ struct ContractedForest {
   }
 };
 ContractedForest contract_forest_host(const fd_forest_params& p, const fd_tree_arrays& t);
+
+// The dense chunk layout of a contracted forest (ensemble.hip dense_layout_host; include/fdengine.h
+// fd_dense_layout_host documents the chunk table and the node word): what ensemble_kernel's VD 3 instantiation walks.
+constexpr int kDenseSMax = 8;  // bundles per chunk at most: the leaf-index tiles are kDenseSMax x 2 KiB, twice
+struct DenseLayout {
+  std::vector<char> blob;           // the chunks, back to back
+  std::vector<int64_t> chunk_off;   // per chunk: byte offset in blob
+  std::vector<int32_t> chunk_len;   // per chunk: bytes (data rounded up to 1 KiB + the 1 KiB table)
+  std::vector<fd_dense_tree> tree;  // per tree, forest order
+  int tpg = 0;                      // trees per bundle
+  uint32_t buf = 0;                 // the chunk buffer's data bytes (EnsCfg::BUF)
+  long long steps = 0;              // sum of the walked depths of the forest's own trees
+};
+// tables[f]: feature f's ascending distinct thresholds (f32) that node words index; mode 3 consecutive bundles, 4 the
+// chunk's trees sorted by depth; owner_bias: sixteenths of a level per tree of the chunk charged to tree group 0
+DenseLayout dense_layout_host(const ContractedForest& c, bool xgb, const std::vector<std::vector<float>>& tables,
+                              bool wide, int mode, int owner_bias);
 
 // card-hash routing records (route.hip): one transaction (48 B) / one result (24 B)
 struct __attribute__((aligned(16))) RouteRecord {
@@ -725,9 +745,11 @@ struct Engine {
   int forest_variant = 0;  // "forest_kernel" option
   bool ens_owner_fixed = true;  // "ensemble_owner" option (A/B of the fused kernel's chunk-owner schedule)
   int ens_chunks = 0;           // "ensemble_chunks": 0 auto, 1 wide, 2 compact chunk layout (ensemble.hip)
-  int ens_contract = 1;         // "ensemble_contract": compact / split rows walk the forests contracted against the
-                                // constant slots: 0 no, 1 (default) each tree to its wave's deepest, 2 to its own depth
+  int ens_contract = 4;         // "ensemble_contract": compact / split rows walk the forests contracted against the
+                                // constant slots: 0 no, 1 each tree to its wave's deepest, 2 to its own depth, 3 / 4
+                                // the dense chunk stream (bundles of consecutive trees / 4, default: sorted by depth)
   unsigned long long ens_contract_total = 0;  // counter "ensemble_contracted_launches"
+  int ens_dense_chunks_last = 0;  // counter "ensemble_dense_chunks": chunks of the last fused pair launch, if dense
   long long ens_steps_last = 0;  // counter "ensemble_node_steps_per_txn": node steps per transaction of the last fused launch
   int mlp_form = 0;        // "mlp_form" option: 0 auto, 1 the LDS form (mlp_lds_kernel) for the reference shape too
   int mlp_wgs_per_cu = 0;  // "mlp_wgs_per_cu" option: the MLP's persistent grid, workgroups per CU (0 auto: 2 where they fit)

@@ -71,6 +71,17 @@ class fd_blend_params(C.Structure):
     ]
 
 
+class fd_dense_tree(C.Structure):
+    _fields_ = [("chunk", C.c_int32), ("bundle", C.c_int32), ("group", C.c_int32), ("depth", C.c_int32),
+                ("node_offset", C.c_int32), ("leaf_offset", C.c_int32)]
+
+
+class fd_dense_info(C.Structure):
+    _fields_ = [("n_chunks", C.c_int32), ("s_max", C.c_int32), ("trees_per_bundle", C.c_int32),
+                ("buf_bytes", C.c_int32), ("blob_bytes", C.c_int64), ("n_thresholds", C.c_int64),
+                ("node_steps", C.c_int64)]
+
+
 class fd_pack_info(C.Structure):
     _fields_ = [
         ("n_trees", C.c_int32),
@@ -408,6 +419,8 @@ SIGNATURES = {
                                       C.POINTER(fd_pack_info)]),
     "fd_contract_forest_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), C.POINTER(_i64),
                                           C.POINTER(fd_tree_arrays), C.POINTER(C.c_int32), C.POINTER(_i64)]),
+    "fd_dense_layout_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), _i32, _i32, _i32,
+                                       C.POINTER(fd_dense_info), _vp, _vp, _vp, _vp, _vp, _vp]),
     "fd_pack_forest_binned_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), _vp, _i64,
                                              _vp, _i64, _vp, C.POINTER(fd_pack_info)]),
     "fd_pack_forest_sparse_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), _vp, _i64,

@@ -838,6 +838,28 @@ def contract_forest_host(fa: ForestArrays):
     return out, depths, pruned.value
 
 
+def dense_layout_host(fa: ForestArrays, wide: bool = True, mode: int = 4, owner_bias: int = 0):
+    """Host-only (no GPU): the dense chunk layout of the contracted forest, as the fused kernel walks it under
+    ensemble_contract 3 / 4 (fd_dense_layout_host; the chunk table and the node word: include/fdengine.h) -> dict of
+    blob (uint8), chunk_offsets (int64), chunk_lengths (int32), trees (structured: chunk, bundle, group, depth,
+    node_offset, leaf_offset), thresholds (f32) with thr_offsets (int32 [num_feature + 1]), and info (fd_dense_info)."""
+    p, t, keep = fa.c_structs()
+    info = N.fd_dense_info()
+    args = (C.byref(p), C.byref(t), int(bool(wide)), int(mode), int(owner_bias), C.byref(info))
+    N.call("fd_dense_layout_host", *args, None, None, None, None, None, None)
+    blob = np.zeros(info.blob_bytes, np.uint8)
+    offs = np.zeros(info.n_chunks, np.int64)
+    lens = np.zeros(info.n_chunks, np.int32)
+    trees = np.zeros(fa.n_trees, np.dtype([(k, np.int32) for k in ("chunk", "bundle", "group", "depth", "node_offset",
+                                                                   "leaf_offset")]))
+    thr = np.zeros(info.n_thresholds, np.float32)
+    thr_off = np.zeros(fa.num_feature + 1, np.int32)
+    N.call("fd_dense_layout_host", *args, *[C.c_void_p(x.ctypes.data) for x in (blob, offs, lens, trees, thr, thr_off)])
+    del keep
+    return dict(blob=blob, chunk_offsets=offs, chunk_lengths=lens, trees=trees, thresholds=thr, thr_offsets=thr_off,
+                info=info)
+
+
 def pack_forest_binned_host(fa: ForestArrays):
     """Host-only binned repack (no GPU): -> (blob bytes, thresholds f32, offsets int32, fd_pack_info).
     Raises NativeError(FD_ERR_UNSUPPORTED) when a feature has more than 65534 distinct thresholds."""
