@@ -642,6 +642,104 @@ int fd_ab_record_ref_host(const uint8_t* variant, const double* prediction, cons
                           const double* processing_time_ms, double time_scalar, const uint8_t* actual_fraud, int64_t n,
                           fd_ab_state* state);
 
+/* ---------------------------------------------------------------- prediction metrics (MetricsCollector) */
+/* Replaces MetricsCollector (ml/monitoring/metrics.py:30-431, called once per scored transaction by ml/main.py): the
+   counters, Prometheus series and "last hour / last minute" figures of record_prediction, reduced on the device from
+   the columns a scoring call leaves there. One collector per engine; not part of fd_state_snapshot.
+   A row is fraud_prob p (f64), decision (enum fd_decision; another code is counted in the totals and under no
+   decision), processing_time_ms (a column, or one scalar for the batch) and, per model m < n_models, model m's own
+   probability model_probs[m * n + row] (NaN: the row has no such model; the layout fd_ab_score_matrix_* writes).
+   Every compare is an f64 compare against the reference's literal; a histogram bucket is the first bound with
+   value <= bound, the duration value being the f64 quotient processing_time_ms / 1000.0.
+   Windows. A record call carries one timestamp (seconds, f64) for all its rows. The state holds a ring of `slots`
+   time slots, each one timestamp and the window accumulators of the rows recorded under it: a call whose timestamp
+   equals the newest slot's merges into it, a greater one opens the next slot (evicting the oldest when the ring is
+   full; the summary counts evictions), a smaller one is FD_ERR_INVALID_ARG. A query at `now` reduces, oldest to
+   newest, the slots with now - ts <= 3600.0 (hour) and <= 60.0 (minute), the reference's predicates (:233, :247).
+   Counts are integer adds and exact. Float sums are pairs hi + lo kept by error-free additions, reduced in an order
+   fixed by n and the calls alone: the same calls on the same state give the same bits (no float atomics), and
+   fd_metrics_record_ref_host reduces in the kernel's order, so host and device agree to the bit call for call. */
+#define FD_METRICS_MAX_MODELS 8
+#define FD_METRICS_SERIES (FD_METRICS_MAX_MODELS + 1) /* "ensemble", then model 0..7 */
+#define FD_METRICS_SCORE_BUCKETS 12 /* le 0.0, 0.1, ..., 1.0, +Inf (:95) */
+#define FD_METRICS_TIME_BUCKETS 12  /* le 0.001, 0.005, 0.01, 0.025, 0.05, 0.1, 0.25, 0.5, 1.0, 2.5, 5.0, +Inf (:89) */
+#define FD_METRICS_RISK_LEVELS 5    /* enum fd_risk */
+typedef struct {
+  int32_t n_models; /* 0..FD_METRICS_MAX_MODELS: the most model columns a record call may carry */
+  int32_t slots;    /* ring size, 1..65536 */
+} fd_metrics_params;
+typedef struct {
+  double hi, lo; /* the sum is hi + lo */
+} fd_metrics_sum;
+/* One model_name label of ml_predictions_total / ml_prediction_duration_seconds (:168-176), cumulative */
+typedef struct {
+  int64_t rows;                               /* duration histogram _count; model_performance[..]["predictions"] :163 */
+  int64_t decisions[4];                       /* ml_predictions_total{model_name, decision}, by enum fd_decision */
+  int64_t time_hist[FD_METRICS_TIME_BUCKETS]; /* per bucket, not cumulated: processing_time_ms / 1000.0 :169, :176 */
+  fd_metrics_sum time_ms;                     /* model_performance[..]["total_time_ms"] :164 */
+  fd_metrics_sum seconds;                     /* duration histogram _sum: the sum of the quotients */
+  double last_timestamp;                      /* model_performance[..]["last_prediction"] :165; 0 without rows */
+} fd_metrics_series;
+typedef struct {
+  int64_t predictions;                          /* prediction_count :153 */
+  int64_t fraud_detections;                     /* p > 0.5 :155 */
+  int64_t declined;                             /* decision == DECLINE :158 */
+  int64_t score_hist[FD_METRICS_SCORE_BUCKETS]; /* ml_fraud_score_distribution per bucket, not cumulated :170 */
+  int64_t risk_detected[FD_METRICS_RISK_LEVELS]; /* ml_fraud_detected_total{risk_level}: p > 0.5 only :178-181, levels :310-321 */
+  fd_metrics_sum score_sum;                     /* ml_fraud_score_distribution _sum */
+  fd_metrics_series series[FD_METRICS_SERIES];  /* [0] "ensemble", [1 + m] model m */
+} fd_metrics_cumulative;
+/* One model over a window (get_model_performance_report :337-364), over the window's rows that carry the model */
+typedef struct {
+  int64_t rows;               /* total_predictions :354 */
+  int64_t dist[3];            /* low_risk p < 0.3, medium_risk 0.3 <= p < 0.7, high_risk p >= 0.7 :360-362 */
+  fd_metrics_sum time_ms;     /* avg_processing_time_ms = sum / rows :355 */
+  fd_metrics_sum prediction;  /* avg_prediction_score = sum / rows :358 */
+  double min_time_ms, max_time_ms; /* :356-357; 0 without rows */
+} fd_metrics_window_model;
+typedef struct {
+  int64_t rows;           /* predictions_last_hour / _last_minute :287-288, :235 */
+  int64_t fraud;          /* p > 0.5: fraud_detections_last_hour :256, :292 */
+  int64_t high_risk;      /* p > 0.8: high_risk_transactions :293 */
+  fd_metrics_sum time_ms; /* avg_processing_time_ms = sum / rows :260 */
+  fd_metrics_window_model model[FD_METRICS_MAX_MODELS];
+} fd_metrics_window;
+typedef struct {
+  fd_metrics_cumulative total;
+  fd_metrics_window hour, minute; /* slots with now - ts <= 3600.0 / <= 60.0 */
+  int64_t evictions;              /* slots dropped from a full ring since init / clear */
+  int64_t slots_used;
+  double newest;                  /* the newest slot's timestamp; 0 when none */
+} fd_metrics_summary;
+/* init: (re)creates an empty collector (FD_ERR_INVALID_ARG for n_models or slots out of range); clear empties it.
+   FD_ERR_NOT_LOADED before fd_metrics_init (as in the calls below that take an engine). */
+int fd_metrics_init(fd_engine* eng, const fd_metrics_params* params);
+int fd_metrics_clear(fd_engine* eng);
+/* n rows under one timestamp. _device: device pointers (the outputs of fd_score_matrix_device /
+   fd_ab_score_matrix_device as they are), enqueued on the engine stream, waits for nothing. d_model_probs may be NULL
+   when n_models is 0; d_time_ms NULL: time_scalar for every row. n < 2^31; n == 0 does nothing.
+   _host: columns in pageable memory have been read when the call returns; columns in pinned (page-locked) memory are
+   read asynchronously and must not change or be freed before fd_engine_sync or fd_metrics_query_host. */
+int fd_metrics_record_device(fd_engine* eng, const double* d_fraud_prob, const uint8_t* d_decision,
+                             const double* d_model_probs, int32_t n_models, const double* d_time_ms,
+                             double time_scalar, double timestamp, int64_t n);
+int fd_metrics_record_host(fd_engine* eng, const double* fraud_prob, const uint8_t* decision,
+                           const double* model_probs, int32_t n_models, const double* time_ms, double time_scalar,
+                           double timestamp, int64_t n);
+/* the summary at `now` (waits for the engine stream; one struct is read back, never the ring) */
+int fd_metrics_query_host(fd_engine* eng, double now, fd_metrics_summary* out);
+/* No device, no engine: the same collector in caller memory of fd_metrics_state_bytes(slots) bytes (0 for slots out
+   of range), by the functions the kernels' lanes use and in the kernels' order of reduction. state_init_host makes it
+   empty. summary_merge_host: out = a then b (out may be a or b): counts add, sums add error-free, min / max / last
+   combine; it joins the summaries of a sharded deployment's ranks taken at one `now`. */
+int64_t fd_metrics_state_bytes(int32_t slots);
+int fd_metrics_state_init_host(void* state, const fd_metrics_params* params);
+int fd_metrics_record_ref_host(void* state, const double* fraud_prob, const uint8_t* decision,
+                               const double* model_probs, int32_t n_models, const double* time_ms, double time_scalar,
+                               double timestamp, int64_t n);
+int fd_metrics_query_ref_host(const void* state, double now, fd_metrics_summary* out);
+int fd_metrics_summary_merge_host(const fd_metrics_summary* a, const fd_metrics_summary* b, fd_metrics_summary* out);
+
 /* The whole hot path for one micro-batch of transactions: fd_features_* (card state read/update,
    scoring vectors) then fd_score_matrix_* on those vectors (ld = FD_VECTOR_WIDTH). d_vectors may be
    NULL (engine scratch). Equivalent to the reference's per-transaction chain

@@ -444,6 +444,7 @@ int fd_engine_destroy(fd_engine* eng) {
   fd::graph_release(e);
   fd::text_release(e);
   fd::ab_release(e);
+  fd::metrics_release(e);
   for (auto* b : {&e.route_blk, &e.route_blk_stream, &e.route_out, &e.route_err, &e.seq_buf, &e.seq_desc, &e.lstm.wpk, &e.lstm.wpk4, &e.lstm.bias,
                   &e.lstm.wout, &e.lstm.bout, &e.state.seq, &e.mlp.blob})
     b->release();
@@ -2380,6 +2381,160 @@ int fd_ab_record_ref_host(const uint8_t* variant, const double* prediction, cons
     fd::ab_add_row(state->variant[variant[i] ? 1 : 0], prediction[i], decision[i],
                    processing_time_ms ? processing_time_ms[i] : time_scalar,
                    actual_fraud ? actual_fraud[i] : (uint8_t)FD_AB_NO_LABEL);
+  FD_API_END
+}
+
+int fd_metrics_init(fd_engine* eng, const fd_metrics_params* params) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "null metrics params");
+  fd::metrics_init(e, *params);
+  FD_API_END
+}
+
+int fd_metrics_clear(fd_engine* eng) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  fd::metrics_clear(E(eng));
+  FD_API_END
+}
+
+int fd_metrics_record_device(fd_engine* eng, const double* d_fraud_prob, const uint8_t* d_decision,
+                             const double* d_model_probs, int32_t n_models, const double* d_time_ms,
+                             double time_scalar, double timestamp, int64_t n) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  fd::metrics_record(E(eng), d_fraud_prob, d_decision, d_model_probs, n_models, d_time_ms, time_scalar, timestamp, n);
+  FD_API_END
+}
+
+int fd_metrics_record_host(fd_engine* eng, const double* fraud_prob, const uint8_t* decision,
+                           const double* model_probs, int32_t n_models, const double* time_ms, double time_scalar,
+                           double timestamp, int64_t n) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  fd::metrics_live(e);
+  fd::metrics_check_record(e.metrics.h, fraud_prob, decision, model_probs, n_models, timestamp, n);
+  if (n == 0) return FD_OK;
+  Stage st(e);
+  const double *dp, *dm, *dt;
+  const uint8_t* dd;
+  st.in(dp, fraud_prob, (size_t)n);
+  st.in(dd, decision, (size_t)n);
+  st.in(dm, n_models ? model_probs : nullptr, (size_t)n * n_models);
+  st.in(dt, time_ms, (size_t)n);
+  st.upload();
+  // No wait, as in fd_ab_record_host: fd_metrics_query_host is ordered behind the kernel on e.stream; pageable
+  // columns have been read when hipMemcpyAsync returns, pinned ones must stay until the stream has passed this call.
+  fd::metrics_record(e, dp, dd, dm, n_models, dt, time_scalar, timestamp, n);
+  FD_API_END
+}
+
+int fd_metrics_query_host(fd_engine* eng, double now, fd_metrics_summary* out) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  fd::metrics_query(E(eng), now, out);
+  FD_API_END
+}
+
+int64_t fd_metrics_state_bytes(int32_t slots) {
+  return slots >= 1 && slots <= 65536 ? (int64_t)fd::metrics_state_bytes(slots) : 0;
+}
+
+int fd_metrics_state_init_host(void* state, const fd_metrics_params* params) {
+  FD_API_BEGIN
+  FD_REQUIRE(state && params, FD_ERR_INVALID_ARG, "null state / params");
+  fd::metrics_check_params(*params);
+  std::memset(state, 0, fd::metrics_state_bytes(params->slots));
+  static_cast<fd::MetricsState*>(state)->h = fd::MetricsHeader{params->slots, params->n_models, 0, 0, 0, 0.0};
+  FD_API_END
+}
+
+int fd_metrics_record_ref_host(void* state, const double* fraud_prob, const uint8_t* decision,
+                               const double* model_probs, int32_t n_models, const double* time_ms, double time_scalar,
+                               double timestamp, int64_t n) {
+  FD_API_BEGIN
+  FD_REQUIRE(state, FD_ERR_INVALID_ARG, "null state");
+  fd::MetricsState& s = *static_cast<fd::MetricsState*>(state);
+  FD_REQUIRE(s.h.slots > 0, FD_ERR_NOT_LOADED, "metrics state not initialised (fd_metrics_state_init_host)");
+  fd::metrics_check_record(s.h, fraud_prob, decision, model_probs, n_models, timestamp, n);
+  if (n == 0) return FD_OK;
+  bool fresh;
+  fd::MetricsSlot& slot = s.ring[fd::metrics_ring_advance(s.h, timestamp, fresh)];
+  if (fresh) {
+    std::memset(&slot, 0, sizeof(slot));
+    slot.ts = timestamp;
+    fd::metrics_window_floats_open(slot.w);
+  }
+  int64_t cnt[fd::kMcCount] = {};
+  fd::MetricsPart part;
+  fd::metrics_rows_host(fraud_prob, decision, model_probs, n_models, time_ms, time_scalar, n, cnt, part);
+  for (int k = 0; k < fd::kMcCount; ++k) {
+    if (cnt[k] == 0) continue;
+    *fd::metrics_counter_ptr(&s.cum, &slot.w, k) += cnt[k];
+    const int sr = fd::metrics_counter_series(k);
+    if (sr >= 0) s.cum.series[sr].last_timestamp = timestamp;
+  }
+  fd::metrics_apply(s.cum, slot.w, part);
+  FD_API_END
+}
+
+int fd_metrics_query_ref_host(const void* state, double now, fd_metrics_summary* out) {
+  FD_API_BEGIN
+  FD_REQUIRE(state && out, FD_ERR_INVALID_ARG, "null state / out");
+  const fd::MetricsState& s = *static_cast<const fd::MetricsState*>(state);
+  FD_REQUIRE(s.h.slots > 0, FD_ERR_NOT_LOADED, "metrics state not initialised (fd_metrics_state_init_host)");
+  std::memset(out, 0, sizeof(*out));
+  out->total = s.cum;
+  for (int g = 0; g <= FD_METRICS_MAX_MODELS; ++g) {
+    fd::metrics_window_reduce_group(s.ring, s.h.slots, s.h.head, s.h.used, now, 3600.0, g, out->hour);
+    fd::metrics_window_reduce_group(s.ring, s.h.slots, s.h.head, s.h.used, now, 60.0, g, out->minute);
+  }
+  out->evictions = s.h.evictions;
+  out->slots_used = s.h.used;
+  out->newest = s.h.used ? s.h.newest : 0.0;
+  FD_API_END
+}
+
+// b's window into a's: metrics_window_merge_group with the "no rows: min = max = 0" form of a summary
+static void metrics_summary_window_merge(fd_metrics_window& a, const fd_metrics_window& b) {
+  fd::metrics_window_merge_group(a, b, 0);
+  for (int m = 0; m < FD_METRICS_MAX_MODELS; ++m) {
+    fd_metrics_window_model& am = a.model[m];
+    const fd_metrics_window_model& bm = b.model[m];
+    if (bm.rows == 0) continue;
+    if (am.rows == 0) {
+      am = bm;
+      continue;
+    }
+    fd::metrics_window_merge_group(a, b, 1 + m);
+  }
+}
+
+int fd_metrics_summary_merge_host(const fd_metrics_summary* a, const fd_metrics_summary* b, fd_metrics_summary* out) {
+  FD_API_BEGIN
+  FD_REQUIRE(a && b && out, FD_ERR_INVALID_ARG, "null summary");
+  fd_metrics_summary r = *a;
+  const fd_metrics_summary& o = *b;
+  for (int k = 0; k < fd::kMcCumCount; ++k) (&r.total.predictions)[k] += (&o.total.predictions)[k];
+  fd::metrics_sum_merge(r.total.score_sum, o.total.score_sum);
+  for (int s = 0; s < FD_METRICS_SERIES; ++s) {
+    fd_metrics_series& rs = r.total.series[s];
+    const fd_metrics_series& os = o.total.series[s];
+    if (os.rows == 0) continue;
+    rs.last_timestamp = rs.rows == 0 ? os.last_timestamp : fd::metrics_max(rs.last_timestamp, os.last_timestamp);
+    for (int k = 0; k < fd::kMcSeriesCount; ++k) (&rs.rows)[k] += (&os.rows)[k];
+    fd::metrics_sum_merge(rs.time_ms, os.time_ms);
+    fd::metrics_sum_merge(rs.seconds, os.seconds);
+  }
+  metrics_summary_window_merge(r.hour, o.hour);
+  metrics_summary_window_merge(r.minute, o.minute);
+  r.evictions += o.evictions;
+  r.slots_used += o.slots_used;
+  r.newest = a->slots_used == 0 ? o.newest : o.slots_used == 0 ? r.newest : fd::metrics_max(r.newest, o.newest);
+  *out = r;
   FD_API_END
 }
 

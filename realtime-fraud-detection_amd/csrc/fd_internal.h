@@ -17,6 +17,7 @@
 
 #include "fdengine.h"
 #include "key_hash.h"
+#include "metrics_row.h"
 
 namespace fd {
 
@@ -360,6 +361,14 @@ struct AbState {
   DeviceBuffer index;     // fd_ab_score_matrix_* (engine.hip): the partition's index, its two counts, the variants
   DeviceBuffer rows;      // ... and the batch in partition order with its results
 };
+// Prediction metrics (metrics.hip): the collector's state on the device, the ring's header on the host
+struct MetricsCollector {
+  bool live = false;
+  MetricsHeader h{};
+  DeviceBuffer state;     // MetricsState (its header unused)
+  DeviceBuffer partials;  // one MetricsPart per workgroup of the record kernel, then its ticket
+  DeviceBuffer summary;   // the query kernel's fd_metrics_summary
+};
 // ab_scatter_results: partition-order results (p_*) back to arrival order; a null output is skipped
 struct AbScatter {
   const int32_t* idx;
@@ -658,6 +667,7 @@ struct Engine {
   GraphState graph;
   TextState text;
   AbState ab;
+  MetricsCollector metrics;
   WindowState windows;
   IngestTables ingest;
   SinkState sink;
@@ -955,6 +965,18 @@ void ab_scatter_results(Engine& e, const AbScatter& a);
 void ab_record(Engine& e, int id, const uint8_t* d_variant, const double* d_prediction, const uint8_t* d_decision,
                const double* d_time_ms, double time_scalar, const uint8_t* d_label, int64_t n);
 void ab_state_read(Engine& e, int id, fd_ab_state* out);  // waits for the engine stream
+// metrics.hip (device pointers, on e.stream)
+size_t metrics_state_bytes(int32_t slots);
+void metrics_check_params(const fd_metrics_params& p);  // FD_ERR_INVALID_ARG
+void metrics_live(Engine& e);                           // FD_ERR_NOT_LOADED before metrics_init
+void metrics_init(Engine& e, const fd_metrics_params& p);
+void metrics_clear(Engine& e);
+void metrics_release(Engine& e);
+void metrics_check_record(const MetricsHeader& h, const void* fraud_prob, const void* decision,
+                          const void* model_probs, int32_t n_models, double timestamp, int64_t n);
+void metrics_record(Engine& e, const double* d_fraud_prob, const uint8_t* d_decision, const double* d_model_probs,
+                    int32_t n_models, const double* d_time_ms, double time_scalar, double timestamp, int64_t n);
+void metrics_query(Engine& e, double now, fd_metrics_summary* out);  // waits for the engine stream
 // model_io.hip: the unchanged XGBoost 2.0.3 JSON model file, flattened (fdengine/forest.py semantics)
 struct XgbModel {
   int num_feature = 0;

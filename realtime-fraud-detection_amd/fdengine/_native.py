@@ -188,6 +188,55 @@ class fd_ab_model_set(C.Structure):
     _fields_ = [("params", C.c_void_p), ("slots", C.c_void_p), ("ext_probs", C.c_void_p), ("present", C.c_void_p)]
 
 
+FD_METRICS_MAX_MODELS = 8
+FD_METRICS_SERIES = FD_METRICS_MAX_MODELS + 1
+FD_METRICS_SCORE_BUCKETS = 12
+FD_METRICS_TIME_BUCKETS = 12
+FD_METRICS_RISK_LEVELS = 5
+# the finite upper bounds of the two histograms (ml/monitoring/metrics.py:89, :95); the last bucket is +Inf
+METRICS_SCORE_BOUNDS = (0.0, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 1.0)
+METRICS_TIME_BOUNDS = (0.001, 0.005, 0.01, 0.025, 0.05, 0.1, 0.25, 0.5, 1.0, 2.5, 5.0)
+
+
+class fd_metrics_params(C.Structure):
+    _fields_ = [("n_models", C.c_int32), ("slots", C.c_int32)]
+
+
+class fd_metrics_sum(C.Structure):
+    _fields_ = [("hi", C.c_double), ("lo", C.c_double)]
+
+    @property
+    def value(self) -> float:
+        return self.hi + self.lo
+
+
+class fd_metrics_series(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("decisions", C.c_int64 * 4), ("time_hist", C.c_int64 * FD_METRICS_TIME_BUCKETS),
+                ("time_ms", fd_metrics_sum), ("seconds", fd_metrics_sum), ("last_timestamp", C.c_double)]
+
+
+class fd_metrics_cumulative(C.Structure):
+    _fields_ = [("predictions", C.c_int64), ("fraud_detections", C.c_int64), ("declined", C.c_int64),
+                ("score_hist", C.c_int64 * FD_METRICS_SCORE_BUCKETS),
+                ("risk_detected", C.c_int64 * FD_METRICS_RISK_LEVELS), ("score_sum", fd_metrics_sum),
+                ("series", fd_metrics_series * FD_METRICS_SERIES)]
+
+
+class fd_metrics_window_model(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("dist", C.c_int64 * 3), ("time_ms", fd_metrics_sum),
+                ("prediction", fd_metrics_sum), ("min_time_ms", C.c_double), ("max_time_ms", C.c_double)]
+
+
+class fd_metrics_window(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("fraud", C.c_int64), ("high_risk", C.c_int64), ("time_ms", fd_metrics_sum),
+                ("model", fd_metrics_window_model * FD_METRICS_MAX_MODELS)]
+
+
+class fd_metrics_summary(C.Structure):
+    _fields_ = [("total", fd_metrics_cumulative), ("hour", fd_metrics_window), ("minute", fd_metrics_window),
+                ("evictions", C.c_int64), ("slots_used", C.c_int64), ("newest", C.c_double)]
+
+
 class fd_users(C.Structure):
     _fields_ = [("n", C.c_int64), ("key", C.c_void_p), ("avg_amount", C.c_void_p),
                 ("account_age_days", C.c_void_p), ("device_fp", C.c_void_p)]
@@ -372,6 +421,17 @@ SIGNATURES = {
     "fd_ab_state_merge_host": (C.c_int, [C.POINTER(fd_ab_state), C.POINTER(fd_ab_state), C.POINTER(fd_ab_state)]),
     "fd_ab_bucket_host": (C.c_int, [_vp, _i64, C.c_uint64, _vp]),
     "fd_ab_record_ref_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, _vp, _i64, C.POINTER(fd_ab_state)]),
+    "fd_metrics_init": (C.c_int, [_vp, C.POINTER(fd_metrics_params)]),
+    "fd_metrics_clear": (C.c_int, [_vp]),
+    "fd_metrics_record_device": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, C.c_double, C.c_double, _i64]),
+    "fd_metrics_record_host": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, C.c_double, C.c_double, _i64]),
+    "fd_metrics_query_host": (C.c_int, [_vp, C.c_double, C.POINTER(fd_metrics_summary)]),
+    "fd_metrics_state_bytes": (_i64, [_i32]),
+    "fd_metrics_state_init_host": (C.c_int, [_vp, C.POINTER(fd_metrics_params)]),
+    "fd_metrics_record_ref_host": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, C.c_double, C.c_double, _i64]),
+    "fd_metrics_query_ref_host": (C.c_int, [_vp, C.c_double, C.POINTER(fd_metrics_summary)]),
+    "fd_metrics_summary_merge_host": (C.c_int, [C.POINTER(fd_metrics_summary), C.POINTER(fd_metrics_summary),
+                                                C.POINTER(fd_metrics_summary)]),
     "fd_features_seq_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _vp, _vp, _vp]),
     "fd_shard_of_host": (C.c_int, [_vp, _i64, _i32, _vp]),
     "fd_route_partition_device": (C.c_int, [_vp, C.POINTER(fd_txn_batch), _i64, _i32, _vp, _vp]),

@@ -647,6 +647,47 @@ class FraudEngine:
         N.call("fd_ab_state_host", self._h, int(test_id), C.byref(out))
         return out
 
+    # ------------------------------------------------------------------ prediction metrics (fdengine/monitoring.py)
+    def metrics_init(self, n_models: int = N.FD_METRICS_MAX_MODELS, slots: int = 4096) -> None:
+        """An empty collector on this engine: at most n_models model columns per record call, a ring of `slots` time
+        slots for the hour / minute windows."""
+        p = N.fd_metrics_params(int(n_models), int(slots))
+        N.call("fd_metrics_init", self._h, C.byref(p))
+
+    def metrics_clear(self) -> None:
+        N.call("fd_metrics_clear", self._h)
+
+    def metrics_record(self, fraud_prob, decision, model_probs, processing_time_ms, timestamp: float) -> None:
+        """n rows under one timestamp, from host columns. model_probs: None or f64 [n_models, n] (a model's column is
+        a row of it), NaN where a row has no such model. processing_time_ms: an array, or one float for every row."""
+        fraud_prob = np.ascontiguousarray(fraud_prob, np.float64)
+        n = len(fraud_prob)
+        decision = np.ascontiguousarray(decision, np.uint8)
+        mp = None if model_probs is None else np.ascontiguousarray(model_probs, np.float64).reshape(-1, n)
+        n_models = 0 if mp is None else mp.shape[0]
+        scalar = np.ndim(processing_time_ms) == 0
+        times = None if scalar else np.ascontiguousarray(processing_time_ms, np.float64)
+        for a in (decision, times):
+            if a is not None and len(a) != n:
+                raise ValueError("columns of different lengths")
+        N.call("fd_metrics_record_host", self._h, _ptr(fraud_prob), _ptr(decision), _ptr(mp) if n_models else None,
+               n_models, _ptr(times), float(processing_time_ms) if scalar else 0.0, float(timestamp), n)
+
+    def metrics_record_device(self, fraud_prob_ptr: int, decision_ptr: int, n: int, timestamp: float,
+                              model_probs_ptr: int = 0, n_models: int = 0, time_ptr: int = 0,
+                              time_scalar: float = 0.0) -> None:
+        """Device pointers (fd_score_matrix_device's outputs as they are), on the engine stream, nothing read back.
+        time_ptr 0: time_scalar for every row."""
+        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        N.call("fd_metrics_record_device", self._h, C.c_void_p(fraud_prob_ptr), C.c_void_p(decision_ptr),
+               opt(model_probs_ptr), int(n_models), opt(time_ptr), float(time_scalar), float(timestamp), int(n))
+
+    def metrics_query(self, now: float) -> N.fd_metrics_summary:
+        """The cumulative part and the hour / minute windows at `now` (waits for the engine stream)."""
+        out = N.fd_metrics_summary()
+        N.call("fd_metrics_query_host", self._h, float(now), C.byref(out))
+        return out
+
     # ------------------------------------------------------------------ card-hash sharding (fdengine/sharding.py)
     def route_partition_device(self, txn_ptrs: dict, n: int, n_shards: int, records_ptr: int, counts_ptr: int) -> None:
         """Group one device-resident micro-batch by owner GPU: n records of FD_ROUTE_RECORD_BYTES at
@@ -791,6 +832,19 @@ class FraudEngine:
         N.call("fd_score_matrix_host", self._h, C.byref(params), _ptr(sl), ext, _ptr(pres), _ptr(X), n, ld,
                _ptr(mp), _ptr(fp), _ptr(conf), _ptr(dec), _ptr(risk))
         return mp, fp, conf, dec, risk
+
+    def score_matrix_device(self, params: N.fd_blend_params, slots: Sequence[int], X_ptr: int, n: int, ld: int,
+                            fp_ptr: int, mp_ptr: int = 0, conf_ptr: int = 0, dec_ptr: int = 0,
+                            risk_ptr: int = 0) -> None:
+        """score_matrix on device pointers, every model a loaded forest (slots[m] >= 0): enqueued on the engine
+        stream, nothing read back. mp_ptr: f64 [n_models, n]."""
+        sl = np.array(list(slots) + [-1] * (N.FD_MAX_MODELS - len(slots)), np.int32)
+        if (sl[:params.n_models] < 0).any():
+            raise ValueError("score_matrix_device takes forest slots only")
+        ext = (C.c_void_p * N.FD_MAX_MODELS)()
+        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        N.call("fd_score_matrix_device", self._h, C.byref(params), _ptr(sl), ext, None, C.c_void_p(X_ptr), int(n),
+               int(ld), opt(mp_ptr), C.c_void_p(fp_ptr), opt(conf_ptr), opt(dec_ptr), opt(risk_ptr))
 
     def blend_device(self, params: N.fd_blend_params, n: int, prob_ptrs: Sequence[Optional[int]],
                      fp_ptr: int, conf_ptr: int = 0, dec_ptr: int = 0, risk_ptr: int = 0) -> None:
