@@ -56,8 +56,54 @@ def _code(c):
 
 
 def day_of_month(days: int) -> int:
+    """UTC day of month of a day count since 1970-01-01, proleptic Gregorian, for any count: the calendar repeats
+    every 146 097 days (400 years), so the count is shifted by whole cycles into datetime's range."""
     import datetime
-    return (datetime.date(1970, 1, 1) + datetime.timedelta(days=int(days))).day
+    return (datetime.date(2000, 1, 1) + datetime.timedelta(days=(int(days) - 10957) % 146097)).day
+
+
+def _jsqrt(x):
+    """Math.sqrt: NaN for a negative or NaN argument (math.sqrt raises)"""
+    return NaN if (x != x or x < 0) else math.sqrt(x)
+
+
+def _jsin(x):
+    return NaN if (x != x or math.isinf(x)) else math.sin(x)
+
+
+def _jcos(x):
+    return NaN if (x != x or math.isinf(x)) else math.cos(x)
+
+
+def haversine_a(glat, glon, mlat, mlon):
+    """the `a` of FeatureExtractor.calculateDistance (fl/features/FeatureExtractor.java:407-418)"""
+    rad = 0.017453292519943295
+    dlat, dlon = (mlat - glat) * rad, (mlon - glon) * rad
+    return (_jsin(dlat / 2) * _jsin(dlat / 2)
+            + _jcos(glat * rad) * _jcos(mlat * rad) * _jsin(dlon / 2) * _jsin(dlon / 2))
+
+
+def distance_from_a(a):
+    """6371 * 2 * atan2(sqrt(a), sqrt(1 - a)); NaN where Java's Math.sqrt returns NaN (a < 0, a > 1, NaN)"""
+    return 6371 * (2 * math.atan2(_jsqrt(a), _jsqrt(1 - a)))
+
+
+# the products of the two score chains. A compiler that contracts `c + a * b` into one fused multiply-add rounds
+# once instead of twice; feature_map(contract={...}) restates that for the named products, so that a test can show
+# which rows would notice. Products by a power of two are exact: contracting them changes no bit.
+INEXACT_PRODUCTS = ("amount * 0.2", "temporal * 0.1", "merchant * 0.2", "velocity * 0.15", "device * 0.1",
+                    "existing * 0.6", "feature_based * 0.4", "user_risk * 0.2")
+EXACT_PRODUCTS = ("risk_score * 0.5", "fraud_rate * 2.0 (fe)", "user * 0.25", "fraud_rate * 2.0 (tp)",
+                  "existing * 0.5")
+REORDERINGS = ("fe chain reversed", "tp chain reversed")  # the same terms added last to first
+
+
+def _fma(a, b, c):
+    """a * b + c rounded once"""
+    from fractions import Fraction
+    if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)):
+        return c + a * b
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
 
 
 def _operating(mext, m, h):
@@ -66,11 +112,16 @@ def _operating(mext, m, h):
     return int(mext["open_hour"][m]) <= h < int(mext["close_hour"][m])
 
 
-def feature_map(txns, ctx, raw, vel5, users_ext, merchants, mext, vocab_pay, vocab_refund, threshold=0.7):
+def feature_map(txns, ctx, raw, vel5, users_ext, merchants, mext, vocab_pay, vocab_refund, threshold=0.7,
+                contract=frozenset()):
     """txns: SoA dict (fd_txn_batch fields); ctx: dict of the fd_txn_context arrays (missing keys = null);
     raw, vel5: the oracle feature state's outputs for the same batch; users_ext: {key: dict of profile
     fields}; merchants: {"fraud_rate", "risk_multiplier"}; mext: dict of fd_merchants_ext arrays or None.
+    contract: names from INEXACT_PRODUCTS / EXACT_PRODUCTS computed as one fused multiply-add, or from REORDERINGS
+    (mutants, for tests).
     -> (fmap [n, 64] f64, rules structured array)."""
+    assert set(contract) <= set(INEXACT_PRODUCTS + EXACT_PRODUCTS + REORDERINGS)
+    ma = lambda site, a, b, c: _fma(a, b, c) if site in contract else c + a * b  # noqa: E731
     n = len(raw)
     fm = np.full((n, 64), np.nan)
     rules = np.zeros(n, dtype=[("tp_score", "<f8"), ("fe_score", "<f8"), ("tp_decision", "u1"), ("tp_risk", "u1"),
@@ -146,11 +197,7 @@ def feature_map(txns, ctx, raw, vel5, users_ext, merchants, mext, vocab_pay, voc
             f[22], f[23] = glat, glon
             f[24] = 1.0 if (abs(glat) > 60 or (abs(glat) < 10 and abs(glon) < 10)) else 0.0
             if not math.isnan(mlat) and not math.isnan(mlon):
-                rad = 0.017453292519943295
-                dlat, dlon = (mlat - glat) * rad, (mlon - glon) * rad
-                a = (math.sin(dlat / 2) * math.sin(dlat / 2)
-                     + math.cos(glat * rad) * math.cos(mlat * rad) * math.sin(dlon / 2) * math.sin(dlon / 2))
-                f[25] = 6371 * (2 * math.atan2(math.sqrt(a), math.sqrt(1 - a)))
+                f[25] = distance_from_a(haversine_a(glat, glon, mlat, mlon))
         if has_user and not math.isnan(intl):
             f[26] = intl
             f[27] = 1.0 if intl < 0.1 else 0.0
@@ -221,11 +268,11 @@ def feature_map(txns, ctx, raw, vel5, users_ext, merchants, mext, vocab_pay, voc
         if T(30): su += 0.4
         elif T(29): su += 0.2
         if F(32): su += 0.3
-        if not math.isnan(f[31]): su += f[31] * 0.5
+        if not math.isnan(f[31]): su = ma("risk_score * 0.5", f[31], 0.5, su)
         sm = 0.0
         if T(40): sm += 0.8
         if T(42): sm += 0.3
-        if not math.isnan(f[39]): sm += f[39] * 2.0
+        if not math.isnan(f[39]): sm = ma("fraud_rate * 2.0 (fe)", f[39], 2.0, sm)
         if T(45): sm += 0.2
         if F(43): sm += 0.15
         sv = 0.0
@@ -238,15 +285,24 @@ def feature_map(txns, ctx, raw, vel5, users_ext, merchants, mext, vocab_pay, voc
         if not math.isnan(f[49]): sd += f[49]
         if T(50): sd += 0.2
         fb = 0.0
-        fb += sa * 0.2
-        fb += st * 0.1
-        fb += su * 0.25
-        fb += sm * 0.2
-        fb += sv * 0.15
-        fb += sd * 0.1
+        fb = ma("amount * 0.2", sa, 0.2, fb)
+        fb = ma("temporal * 0.1", st, 0.1, fb)
+        fb = ma("user * 0.25", su, 0.25, fb)
+        fb = ma("merchant * 0.2", sm, 0.2, fb)
+        fb = ma("velocity * 0.15", sv, 0.15, fb)
+        fb = ma("device * 0.1", sd, 0.1, fb)
+        if "fe chain reversed" in contract:
+            fb = 0.0
+            for term in (sd * 0.1, sv * 0.15, sm * 0.2, su * 0.25, st * 0.1, sa * 0.2):
+                fb += term
         fb = max(0.0, min(1.0, fb))
         existing = g("fraud_score", i, NaN)
-        fe = fb if math.isnan(existing) else max(0.0, min(1.0, (existing * 0.6) + (fb * 0.4)))
+        if math.isnan(existing):
+            fe = fb
+        elif "existing * 0.6" in contract:
+            fe = max(0.0, min(1.0, _fma(existing, 0.6, fb * 0.4)))
+        else:
+            fe = max(0.0, min(1.0, ma("feature_based * 0.4", fb, 0.4, existing * 0.6)))
         rules["fe_score"][i] = fe
         rules["fe_risk"][i] = CRITICAL if fe >= 0.95 else HIGH if fe >= 0.8 else MEDIUM if fe >= 0.6 else \
             LOW if fe >= 0.3 else VERY_LOW
@@ -256,7 +312,7 @@ def feature_map(txns, ctx, raw, vel5, users_ext, merchants, mext, vocab_pay, voc
         urisk = risk if has_user else 0.5
         uver = verified if has_user else False
         pu = 0.0
-        if not math.isnan(urisk): pu += urisk * 0.2
+        if not math.isnan(urisk): pu = ma("user_risk * 0.2", urisk, 0.2, pu)
         if age_known and age < 30: pu += 0.1
         if not uver: pu += 0.15
         rl = mrl if has_m else 1
@@ -266,7 +322,7 @@ def feature_map(txns, ctx, raw, vel5, users_ext, merchants, mext, vocab_pay, voc
         if rl == 2: pm += 0.2
         elif rl == 1: pm += 0.1
         if bl: pm += 0.4
-        if not math.isnan(fr) and fr > 0.05: pm += fr * 2.0
+        if not math.isnan(fr) and fr > 0.05: pm = ma("fraud_rate * 2.0 (tp)", fr, 2.0, pm)
         if has_m and mhr: pm += 0.15
         pf = 0.0
         if has_user and not math.isnan(uavg) and uavg > 0 and amount / uavg > 5.0: pf += 0.15
@@ -275,9 +331,13 @@ def feature_map(txns, ctx, raw, vel5, users_ext, merchants, mext, vocab_pay, voc
         if hour_field != 255 and not _operating(mext if mloaded else None, m, hour_field): pf += 0.1
         tp = 0.0
         if not math.isnan(existing): tp = existing * 0.5
-        tp += pu
+        tp = ma("existing * 0.5", existing, 0.5, pu) if ("existing * 0.5" in contract and tp != 0.0) else tp + pu
         tp += pm
         tp += pf
+        if "tp chain reversed" in contract:
+            tp = 0.0
+            for term in (pf, pm, pu, 0.0 if math.isnan(existing) else existing * 0.5):
+                tp += term
         tp = max(0.0, min(1.0, tp))
         rules["tp_score"][i] = tp
         if tp >= 0.9: dec, rk = DECLINE, CRITICAL
