@@ -670,9 +670,9 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value) {
     FD_REQUIRE(value >= 0 && value <= 2, FD_ERR_INVALID_ARG, "ensemble_chunks must be 0, 1 or 2");
     e.ens_chunks = (int)value;
   } else if (k == "ensemble_contract") {  // fused kernel on compact / split rows: the forests contracted against the
-    // rows' constant slots (ensemble.hip contract_forest_host). 4 (default) / 3: the contracted trees packed densely,
-    // up to eight bundles per chunk and barrier (dense_layout_host), bundles of the chunk's trees sorted by depth / of
-    // consecutive trees; 1 the padded chunks, each tree walked to the deepest of its wave's trees (a fixed-depth walk
+    // rows' constant slots (ensemble_plan.hip contract_forest_host). 4 (default) / 3: the contracted trees packed
+    // densely, up to eight bundles per chunk and barrier (dense_layout_host), bundles of the chunk's trees sorted by
+    // depth / of consecutive trees; 1 the padded chunks, each tree walked to the deepest of its wave's trees (a fixed-depth walk
     // chosen per wave and chunk); 2 each tree's own depth (uniform branches inside the walk: measured slower, DESIGN
     // §3); 0 the full forests at the common depth. Outputs are identical in every mode. A change rebuilds the plan's
     // chunks: the device is idle first

@@ -4,10 +4,10 @@
 // confidence, weighted / voting / stacking blend, decision, risk), in one launch — instead of a forest
 // kernel per model (each binning the same vectors in its own prologue) plus a blend kernel.
 //
-// Joint repack (host, cached per pair of loaded forests): both forests padded to one depth D <= 8 and their
-// node words rewritten against the MERGED per-feature table of distinct thresholds (union of the two), so
-// one bin word per (feature, transaction) serves both: "x < t" is "bin_merged(x) <= index of t in the
-// merged table" for every threshold of either forest. Leaf ids are not produced on this path (the per-model
+// Joint repack (host, ensemble_plan.hip build_plan, cached per pair of loaded forests): both forests padded to one
+// depth D <= 8 and their node words rewritten against the MERGED per-feature table of distinct thresholds (union
+// of the two), so one bin word per (feature, transaction) serves both: "x < t" is "bin_merged(x) <= index of t in
+// the merged table" for every threshold of either forest. Leaf ids are not produced on this path (the per-model
 // kernels keep the leaf-id outputs).
 //
 // Kernel: 1024 threads = 16 waves per tile (tree group gg = wave >> 2, transaction group wave & 3). Prologue:
@@ -39,170 +39,19 @@
 //     before cutting bundles, 3 keeps consecutive trees.
 //   1 — the padded 1 KiB-block chunks, each wave's trees walked to the deepest of them (walk_pack_var, VD 2);
 //   2 — the same chunks, each tree to its own depth (walk_ens_var, VD 1); 0 — the full forests.
-#include <algorithm>
-#include <atomic>
-#include <cstring>
-
+//
+// This file: the kernel and its launchers. The plans they run — the joint repack, the contraction, the chunk packers
+// and the binning passes — are built on the host by ensemble_plan.hip; ensemble_layout.h holds what the two share
+// (chunk geometry, LDS layout, node word, the dense chunk table).
 #include "blend_row.h"
+#include "ensemble_layout.h"
 #include "walk_common.h"
 
 namespace fd {
 
-static std::atomic<uint64_t> g_forest_gen{0};
-
-void forest_loaded(PackedForest& pf, const fd_forest_params& p, const fd_tree_arrays& t) {
-  pf.gen = ++g_forest_gen;
-  pf.params = p;
-  const int64_t m = t.tree_offsets[t.n_trees];
-  pf.t_off.assign(t.tree_offsets, t.tree_offsets + t.n_trees + 1);
-  pf.t_left.assign(t.left, t.left + m);
-  pf.t_right.assign(t.right, t.right + m);
-  pf.t_feature.assign(t.feature, t.feature + m);
-  pf.t_threshold.assign(t.threshold, t.threshold + m);
-  pf.t_leaf.assign(t.leaf_value, t.leaf_value + m);
-  if (t.default_left)
-    pf.t_dleft.assign(t.default_left, t.default_left + m);
-  else
-    pf.t_dleft.assign((size_t)m, 0);
-}
-
-// Every split on a constant slot of the compact scoring vector decided here, once: the pipelined stream's rows
-// carry 0.5 in slots 12, 24, 25, 33, 34 and 0 in the other 37 that are not among the 22 varying ones (compact_src),
-// so such a node sends every transaction the same way — left iff value < threshold in f32, pack_forest_host's
-// comparison (the constants are never NaN: default_left plays no part) — and it is replaced by that child. Nodes are
-// renumbered in pre-order; leaf values and the tree order are untouched. A tree that resolves to one leaf becomes a
-// root over two leaves of that value (slot 0 against 0, never looked at); a tree that was a lone leaf stays one.
-ContractedForest contract_forest_host(const fd_forest_params& p, const fd_tree_arrays& t) {
-  FD_REQUIRE(p.kind == FD_FOREST_XGB_BINARY_LOGISTIC || p.kind == FD_FOREST_SKLEARN_IFOREST, FD_ERR_INVALID_ARG,
-             "contraction: XGBoost binary:logistic or IsolationForest trees");
-  FD_REQUIRE(p.num_feature > 0 && p.num_feature <= kMaxFeatures, FD_ERR_UNSUPPORTED, "num_feature must be in [1, 64]");
-  FD_REQUIRE(forest_depth_probe(t) >= 0, FD_ERR_INVALID_ARG, "incomplete tree arrays or a tree that is not a tree");
-  const bool xgb = p.kind == FD_FOREST_XGB_BINARY_LOGISTIC;
-  ContractedForest c;
-  c.off.push_back(0);
-  struct Item {
-    int32_t o, lo, ro;  // node, its children after resolution (original ids)
-    int depth;
-  };
-  std::vector<Item> st, keep;
-  std::vector<int32_t> remap;
-  for (int i = 0; i < t.n_trees; ++i) {
-    const int64_t a = t.tree_offsets[i], m = t.tree_offsets[i + 1] - a;
-    const int32_t *L = t.left + a, *R = t.right + a, *F = t.feature + a;
-    auto resolve = [&](int32_t o) {  // down through the constant splits
-      while (L[o] >= 0) {
-        FD_REQUIRE(F[o] >= 0 && F[o] < p.num_feature, FD_ERR_INVALID_ARG, "split feature outside [0, num_feature)");
-        const int src = compact_src(F[o]);
-        if (src >= 0) break;
-        const float val = src == -2 ? 0.5f : 0.0f;
-        const float thr = xgb ? (float)t.threshold[a + o] : sklearn_threshold_to_lt(t.threshold[a + o]);
-        o = val < thr ? L[o] : R[o];
-      }
-      return o;
-    };
-    const int64_t base = (int64_t)c.left.size();
-    auto emit = [&](int32_t l, int32_t r, int32_t f, double thr, uint8_t dl, double leaf) {
-      c.left.push_back(l);
-      c.right.push_back(r);
-      c.feature.push_back(f);
-      c.threshold.push_back(thr);
-      c.dleft.push_back(dl);
-      c.leaf.push_back(leaf);
-      return (int32_t)((int64_t)c.left.size() - 1 - base);
-    };
-    int64_t splits_in = 0, splits_out = 0;
-    for (int64_t o = 0; o < m; ++o) splits_in += L[o] >= 0 ? 1 : 0;
-    int depth = 0;
-    const int32_t root = resolve(0);
-    if (L[root] < 0 && L[0] >= 0) {  // resolved entirely
-      emit(1, 2, 0, 0.0, 0, 0.0);
-      emit(-1, -1, 0, 0.0, 0, t.leaf_value[a + root]);
-      emit(-1, -1, 0, 0.0, 0, t.leaf_value[a + root]);
-      depth = 1;
-    } else {
-      // the surviving nodes keep their relative order (the root first), so a tree with nothing to resolve comes back
-      // as it went in
-      st.clear();
-      st.push_back({root, 0, 0});
-      keep.clear();
-      while (!st.empty()) {
-        Item it = st.back();
-        st.pop_back();
-        depth = std::max(depth, it.depth);
-        if (L[it.o] >= 0) {
-          it.lo = resolve(L[it.o]);
-          it.ro = resolve(R[it.o]);
-          st.push_back({it.ro, 0, 0, it.depth + 1});
-          st.push_back({it.lo, 0, 0, it.depth + 1});
-        }
-        keep.push_back(it);
-      }
-      std::sort(keep.begin() + 1, keep.end(), [](const Item& x, const Item& y) { return x.o < y.o; });
-      remap.assign((size_t)m, -1);
-      for (size_t k = 0; k < keep.size(); ++k) remap[(size_t)keep[k].o] = (int32_t)k;
-      for (const Item& it : keep) {
-        const int32_t o = it.o;
-        if (L[o] < 0) {
-          emit(-1, -1, F[o], t.threshold[a + o], t.default_left ? t.default_left[a + o] : 0, t.leaf_value[a + o]);
-        } else {
-          ++splits_out;
-          emit(remap[(size_t)it.lo], remap[(size_t)it.ro], F[o], t.threshold[a + o],
-               t.default_left ? t.default_left[a + o] : 0, t.leaf_value[a + o]);
-        }
-      }
-    }
-    c.pruned += splits_in - splits_out;
-    c.depth.push_back(std::max(depth, 1));
-    c.off.push_back((int64_t)c.left.size());
-  }
-  return c;
-}
-
 namespace {
 
 constexpr int kEnsWG = 1024;
-constexpr int kMaxPass = 64;
-
-// Trees per chunk, by layout: wide 24 XGBoost (TPG 6) / 16 IsolationForest (TPG 4) trees in 48 KiB chunk
-// buffers; compact 20 (TPG 5) / 12 (TPG 3) in 40 KiB, which leaves the CU the ~20 KiB of LDS an RCCL kernel
-// needs beside the scoring (the sharded step's exchanges co-run with it: with the wide layout they waited for a
-// whole scoring launch to end). A chunk in LDS: CH node blocks of 1 KiB (walk_ens link addressing), then the CH
-// trees' leaf values [CH][2^D]; its buffer is sized for depth 8: max(CHA x (1 KiB + 1 KiB f32), CHB x (1 KiB +
-// 2 KiB f64)).
-template <bool WIDE>
-struct EnsCfg {
-  static constexpr int CHA = WIDE ? 24 : 20;
-  static constexpr int CHB = WIDE ? 16 : 12;
-  static constexpr uint32_t BUF = (uint32_t)(CHA * (1024 + 256 * 4) > CHB * (1024 + 256 * 8) ? CHA * (1024 + 256 * 4)
-                                                                                             : CHB * (1024 + 256 * 8));
-};
-inline uint32_t ens_buf(bool wide) { return wide ? EnsCfg<true>::BUF : EnsCfg<false>::BUF; }
-constexpr uint32_t kEnsTile = 4u * kTile * 8u;  // leaf indices of one chunk: [tree group][txn] u64, a byte per tree
-
-// The bin tile: u16 bins, two features per 1 KiB row — feature f of transaction t at byte
-// (f >> 1) * 1024 + 4 t + 2 (f & 1) — so a node word's bits [15:10] = f >> 1 and bit 1 = f & 1 address it
-// with one AND-OR, and the 64 lanes of a read hit 64 distinct banks whatever features they ask for.
-__host__ __device__ constexpr uint32_t ens_xs_bytes(int nf) { return (uint32_t)((nf + 1) / 2) * 1024u; }
-
-// LDS bytes of the kernel: Xs | bufA | bufB | tile0 | tile1 | accA (f32) | accB (f64) | flags + owner counter,
-// + 1 KiB alignment
-size_t ens_lds(int nf, bool wide) {
-  return (size_t)ens_xs_bytes(nf) + 2 * (size_t)ens_buf(wide) + 2 * (size_t)kEnsTile + kTile * 4 + kTile * 8 + 128 +
-         1024;
-}
-
-// The dense layout (VD 3: contracted forests on compact / split rows, dense_layout_host): the bin tile holds the 22
-// varying slots at their compact indices (11 KiB), each chunk buffer is BUF data bytes + the chunk's 1 KiB table at a
-// fixed place behind them, and a leaf-index tile holds kDenseSMax bundles. Xs | bufA + table | bufB + table | tile0 |
-// tile1 | accA | accB | flags + owner counter, + 1 KiB alignment: 148,608 B wide, 132,224 B compact, 3 KiB under the
-// padded layout's (kDenseSMax 9 would leave 1 KiB, and the two tables take 2).
-constexpr uint32_t kDenseTile = (uint32_t)kDenseSMax * kTile * 8u;
-constexpr uint32_t kDenseTab = 1024, kDenseGroupTab = 64, kDenseTreeTab = 576;  // the chunk table and its parts
-constexpr int kDenseOwnerBias = 0;  // dense_layout_host's owner_bias in the engine's plans
-size_t ens_lds_dense(bool wide) {
-  return (size_t)ens_xs_bytes(kCompactSlots) + 2 * ((size_t)ens_buf(wide) + kDenseTab) + 2 * (size_t)kDenseTile +
-         kTile * 4 + kTile * 8 + 128 + 1024;
-}
 
 struct EnsArgs {
   // Field order: what a wave reads before its first LDS-DMA goes out (rows, pass 0's table image, chunk 0) and the
@@ -254,13 +103,7 @@ struct EnsArgs {
 #endif
 };
 
-// Ensemble node word: j << 16 | (feature >> 1) << 10 | link << 3 | (feature & 1) << 1 | default_left. `link`
-// makes the next pair address one AND-OR: for a node at heap slot i above the last split level, link = i (its
-// children pair is at byte 8 i of the tree's 1 KiB block); at the last split level link = i - 2^(D-1), so the
-// leaf is 2 link + right. One step is then v_cmp (u16 bin against the word's high half: SDWA) + v_cndmask
-// (child) + v_and_or (bin address) + v_and_or (pair address): 4 VALU, 2 LDS reads.
-constexpr uint32_t kLinkMask = 0x3F8u;
-
+// The walk of TPG trees over D levels, one step 4 VALU + 2 LDS reads (the node word: ensemble_layout.h).
 // tb[j]: the LDS address of tree j's node block, aligned to the block's 4 * 2^D bytes (the link OR is exact)
 template <int D, int TPG, bool NAN_AWARE>
 __device__ __forceinline__ void walk_ens_at(uint32_t (&tb)[TPG], uint32_t lane4, uint32_t (&leaf)[TPG]) {
@@ -314,18 +157,10 @@ __device__ __forceinline__ void walk_ens(uint32_t buf, int t0, uint32_t lane4, u
   walk_ens_at<D, TPG, NAN_AWARE>(tb, lane4, leaf);
 }
 
-// Walk this wave's TPG trees of the chunk at `cur` (trees gg*TPG ...) for its 64 transactions; the leaf
-// indices (< 2^D <= 256) packed a byte per tree, in tree order, stored as one u64 per (tree group, txn).
-// (Measured: byte-per-tree stores of a [txn][16] tile cost ~5 us more per 64k batch; skewing the split
-// towards tree group 0 was slower still.)
-template <int D, int TPG>
-__device__ __forceinline__ unsigned long long walk_pack(uint32_t cur, int gg, uint32_t lane4, bool tile_nan) {
+// a wave's TPG leaf indices (< 2^D <= 256) as one u64, a byte per tree in tree order
+template <int TPG>
+__device__ __forceinline__ unsigned long long pack_leaf_bytes(const uint32_t (&leaf)[TPG]) {
   static_assert(TPG <= 8, "a byte per tree in a u64");
-  uint32_t leaf[TPG];
-  if (tile_nan)
-    walk_ens<D, TPG, true>(cur, gg * TPG, lane4, leaf);
-  else
-    walk_ens<D, TPG, false>(cur, gg * TPG, lane4, leaf);
   uint32_t lo = 0, hi = 0;
 #pragma unroll
   for (int j = 0; j < TPG; ++j) {
@@ -333,6 +168,20 @@ __device__ __forceinline__ unsigned long long walk_pack(uint32_t cur, int gg, ui
     else hi |= leaf[j] << (8 * (j - 4));
   }
   return ((unsigned long long)hi << 32) | lo;
+}
+
+// Walk this wave's TPG trees of the chunk at `cur` (trees gg*TPG ...) for its 64 transactions; the leaf
+// indices (< 2^D <= 256) packed a byte per tree, in tree order, stored as one u64 per (tree group, txn).
+// (Measured: byte-per-tree stores of a [txn][16] tile cost ~5 us more per 64k batch; skewing the split
+// towards tree group 0 was slower still.)
+template <int D, int TPG>
+__device__ __forceinline__ unsigned long long walk_pack(uint32_t cur, int gg, uint32_t lane4, bool tile_nan) {
+  uint32_t leaf[TPG];
+  if (tile_nan)
+    walk_ens<D, TPG, true>(cur, gg * TPG, lane4, leaf);
+  else
+    walk_ens<D, TPG, false>(cur, gg * TPG, lane4, leaf);
+  return pack_leaf_bytes<TPG>(leaf);
 }
 
 // The walk over contracted trees (build_plan: every split on a constant slot of the compact vector resolved on the
@@ -393,7 +242,6 @@ __device__ __forceinline__ void walk_ens_var(uint32_t buf, int t0, uint32_t lane
 // wave's trees to the deepest of them, and that depth selects a fixed-depth walk_ens.
 template <int VD, int TPG>
 __device__ __forceinline__ unsigned long long walk_pack_var(uint32_t cur, int gg, uint32_t lane4, bool tile_nan) {
-  static_assert(TPG <= 8, "a byte per tree in a u64");
   uint32_t leaf[TPG];
   int d[TPG];
 #pragma unroll
@@ -429,16 +277,11 @@ __device__ __forceinline__ unsigned long long walk_pack_var(uint32_t cur, int gg
     }
 #undef FD_WALK_DEPTH
   }
-  uint32_t lo = 0, hi = 0;
-#pragma unroll
-  for (int j = 0; j < TPG; ++j) {
-    if (j < 4) lo |= leaf[j] << (8 * j);
-    else hi |= leaf[j] << (8 * (j - 4));
-  }
-  return ((unsigned long long)hi << 32) | lo;
+  return pack_leaf_bytes<TPG>(leaf);
 }
 
-// walk_ens_at, the leaf indices packed a byte per tree as walk_pack's
+// walk_ens_at, the leaf indices packed a byte per tree as walk_pack's (written out, not pack_leaf_bytes: through the
+// call the dense kernels' instructions come out in another order)
 template <int D, int TPG, bool NAN_AWARE>
 __device__ __forceinline__ unsigned long long walk_pack_at(uint32_t (&tb)[TPG], uint32_t lane4) {
   uint32_t leaf[TPG];
@@ -461,13 +304,14 @@ __device__ __forceinline__ void walk_dense(uint32_t cur, uint32_t tab, uint32_t 
                                            bool tile_nan, uint32_t counts) {
   static_assert(TPG <= 6, "six block offsets per bundle entry");
   const int nb = (int)((counts >> (8 * gg)) & 0xFFu);
-  const uint32_t ent = tab + kDenseGroupTab + (uint32_t)gg * 128u;
+  const uint32_t ent = tab + kDenseGroupTab + (uint32_t)gg * kDenseGroupStride;
   u32x4 e = lds_load<u32x4>(ent);
   for (int s = 0; s < nb; ++s) {
     // (the offsets stay in VGPRs, where the block addresses are wanted: only the depth and the tile row are scalar)
     const uint32_t e0 = __builtin_amdgcn_readfirstlane(e.x);
     const uint32_t off[6] = {e.y & 0xFFFFu, e.y >> 16, e.z & 0xFFFFu, e.z >> 16, e.w & 0xFFFFu, e.w >> 16};
-    e = lds_load<u32x4>(ent + (uint32_t)(s + 1) * 16u);  // (past the group's last entry: still inside the table)
+    // (past the group's last entry: still inside the table)
+    e = lds_load<u32x4>(ent + (uint32_t)(s + 1) * kDenseBundleEnt);
     uint32_t tb[TPG];
 #pragma unroll
     for (int j = 0; j < TPG; ++j) tb[j] = cur + off[j];
@@ -562,49 +406,6 @@ __device__ __forceinline__ void owner_sum(uint32_t buf, uint32_t tile, uint32_t 
   lds_store<LeafT>(acc + (uint32_t)txn * (uint32_t)sizeof(LeafT), s);
 }
 
-// LDS-DMA of `bytes` (a multiple of 1 KiB) by nparts waves (this one: part), 1 KiB pieces dealt round-robin;
-// completed by dma_wait() in the issuing waves (measured: the piece order rotated by workgroup, so that the CUs
-// staging the same tables and chunks at once spread over the L2 channels, changed nothing)
-__device__ __forceinline__ void stage_pieces(const char* __restrict__ src, uint32_t dst, int bytes, int nparts,
-                                             int part) {
-  const int lane = threadIdx.x & 63;
-  const int pieces = bytes >> 10;
-  for (int p = part; p < pieces; p += nparts) {
-    const char* g = src + (p << 10) + lane * 16;
-    const uint32_t m0 = __builtin_amdgcn_readfirstlane(dst + ((uint32_t)p << 10));
-    asm volatile(
-        "s_mov_b32 m0, %0\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off"
-        :
-        : "s"(m0), "v"(g)
-        : "memory", "m0");
-  }
-}
-
-// A dense chunk's image (bytes: its data pieces, then its 1 KiB table) into the buffer at dst, the table to its fixed
-// place tab behind the buffer's data bytes; as stage_pieces
-__device__ __forceinline__ void stage_dense(const char* __restrict__ src, uint32_t dst, uint32_t tab, int bytes,
-                                            int nparts, int part) {
-  const int lane = threadIdx.x & 63;
-  const int pieces = bytes >> 10;
-  for (int p = part; p < pieces; p += nparts) {
-    const char* g = src + (p << 10) + lane * 16;
-    const uint32_t m0 = __builtin_amdgcn_readfirstlane(p + 1 < pieces ? dst + ((uint32_t)p << 10) : tab);
-    asm volatile(
-        "s_mov_b32 m0, %0\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off"
-        :
-        : "s"(m0), "v"(g)
-        : "memory", "m0");
-  }
-}
-
-// Staged threshold tables hold element g at word g + g / 32: the binary search's power-of-two strides would
-// otherwise put every lane of a step on one LDS bank (up to 32-way conflicts); one pad word per 32 spreads them.
-__host__ __device__ __forceinline__ int thr_pad(int g) { return g + (g >> 5); }
-
 #ifdef FD_FOREST_PROFILE
 // per (workgroup < 256, wave): cycles in prologue, loop top (leaf stores, DMA issue, owner add), walk + leaf
 // loads, DMA wait + barrier, epilogue (s_memtime; read by fd_debug_ens_profile)
@@ -684,7 +485,7 @@ __device__ __forceinline__ void bin_compact_constants(const EnsArgs& a, uint16_t
 // binned by one lookup in a per-plan table of the bins of 0..31 (staged in LDS), not searched: each thread keeps 3-4
 // searches of its 5-6 (one lockstep group instead of two). A value outside 0..31 or not integral (never, from the
 // engine's own feature kernel) takes its own search, so the bins stay #{t <= v} for any input.
-constexpr int kLutN = 32;  // (kIntSlots, kIntCompact, int_slot: fd_internal.h, the compact row's byte slots)
+// (kLutN: ensemble_layout.h; kIntSlots, kIntCompact, int_slot: fd_internal.h, the compact row's byte slots)
 static_assert(kIntSlots * kLutN == 8 * 32, "EnsArgs::lut");
 // thread Q's compact indices Q + 4 i: the LUT row of each small-integer one (-1: searched), and the searched i's
 constexpr int kIntOf[4][6] = {{-1, 2, -1, 6, -1, -1}, {-1, 3, 5, -1, -1, -1}, {0, 4, -1, -1, -1, -1},
@@ -781,16 +582,16 @@ __device__ __forceinline__ void load_split(const uint4* __restrict__ ra, const u
 
 // CS: the bin tile holds the varying slots only, slot Q + 4 i at its compact index (the dense layout's node words name
 // it), else every feature at its own index
-template <int Q, int L, bool LUT, bool CS = false>
+template <int Q, int L, bool CS = false>
 __device__ __forceinline__ void bin_compact_pass(const EnsArgs& a, const float (&v)[16], uint16_t* Xs,
                                                  int txn, int f0, int f1, bool glob, uint32_t tl, int o0,
                                                  int& anynan, uint32_t lut) {
   constexpr int NV = (kCompactSlots - Q + 3) / 4;  // compact slots Q, Q + 4, ... below kCompactSlots
-  constexpr int NS = LUT ? kNSearched[Q] : NV;
+  constexpr int NS = kNSearched[Q];
   // the small-integer slots: one LDS lookup each
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    const int ks = LUT ? kIntOf[Q][i] : -1;
+    const int ks = kIntOf[Q][i];
     if (ks < 0) continue;
     const int f = kCompactSlot[Q + 4 * i];
     if (!(f >= f0 && f < f1 && f < a.nf)) continue;  // wave-uniform
@@ -824,7 +625,7 @@ __device__ __forceinline__ void bin_compact_pass(const EnsArgs& a, const float (
     int steps = 0;
 #pragma unroll
     for (int k = 0; k < L; ++k) {
-      const int i = LUT ? kSearched[Q][g0 + k < NS ? g0 + k : 0] : (g0 + k < NS ? g0 + k : 0);
+      const int i = kSearched[Q][g0 + k < NS ? g0 + k : 0];
       const int f = kCompactSlot[Q + 4 * i];
       act[k] = g0 + k < NS && f >= f0 && f < f1 && f < a.nf;
       vv[k] = act[k] ? v[i] : 0.f;  // v[i]: compact slot Q + 4 i of the row
@@ -836,7 +637,7 @@ __device__ __forceinline__ void bin_compact_pass(const EnsArgs& a, const float (
     search_lockstep<L>(vv, o, cnt, pos, steps, glob, tl, o0, a.thr);
 #pragma unroll
     for (int k = 0; k < L; ++k) {
-      const int i = LUT ? kSearched[Q][g0 + k < NS ? g0 + k : 0] : (g0 + k < NS ? g0 + k : 0);
+      const int i = kSearched[Q][g0 + k < NS ? g0 + k : 0];
       const int f = kCompactSlot[Q + 4 * i];
       if (act[k]) {
         const bool nan = vv[k] != vv[k];
@@ -851,6 +652,10 @@ __device__ __forceinline__ void bin_compact_pass(const EnsArgs& a, const float (
 // VD != 0 (D = 8): the chunks hold contracted trees of their own depths (walk_pack_var), leaf rows of 2^a.ldepth
 template <int D, int OUT, bool WIDE, bool LUT = true, int VD = 0>
 __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
+  // LUT: the small-integer slots binned through their table, the only form left since the option without it went
+  // (DESIGN §3). The parameter stays: the benchmark and the committed counter profiles name the kernels by their
+  // symbols, fd::(anonymous namespace)::ensemble_kernel<8, OUT, WIDE, true> among them.
+  static_assert(LUT, "ensemble_kernel: only the small-integer table's instantiations exist");
   constexpr int kCHA = EnsCfg<WIDE>::CHA, kCHB = EnsCfg<WIDE>::CHB;
   constexpr uint32_t kEnsBuf = EnsCfg<WIDE>::BUF;
   constexpr int TPGA = kCHA / 4, TPGB = kCHB / 4;
@@ -948,19 +753,15 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
     // search in global memory instead (engine option ensemble_bin_global): nothing staged, so chunk 0's DMA goes out
     if (a.n_pass > 0 && !(a.pass_global & 1ull))
       stage_pieces(a.img + a.img_off[0], bufA, a.img_off[1] - a.img_off[0], kEnsWG / 64, wave);
-    if (early0) {
-      if (DENSE)
-        stage_dense(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, bufA + kEnsBuf, nA > 0 ? a.stride[0] : a.stride[1],
-                    kEnsWG / 64, wave);
-      else
-        stage_chunk_asm(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, nA > 0 ? a.stride[0] : a.stride[1], kEnsWG / 64);
-    }
+    if (early0)
+      stage_pieces<DENSE>(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, nA > 0 ? a.stride[0] : a.stride[1], kEnsWG / 64, wave,
+                          bufA + kEnsBuf);
 #ifdef FD_FOREST_PROFILE
     pr_st[0] = __builtin_amdgcn_s_memtime();
 #endif
     // compact mode: the small-integer slots' bin table into the accumulator area (unused until the chunk loop)
     // (published by the first pass's staging barrier: no barrier of its own)
-    if (LUT && a.compact && tid < kIntSlots * kLutN / 2)
+    if (a.compact && tid < kIntSlots * kLutN / 2)
       lds_store<uint32_t>(accA + (uint32_t)tid * 4u, reinterpret_cast<const uint32_t*>(a.lut)[tid]);
     // (2) per pass: stage its tables, then bin this thread's features of the pass kLock at a time (independent
     // searches in lockstep, so kLock LDS reads are in flight per step) into the u16 tile
@@ -975,25 +776,18 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
           stage_pieces(a.img + a.img_off[p], bufA, a.img_off[p + 1] - a.img_off[p], kEnsWG / 64, wave);
         dma_wait();
         __syncthreads();
-      } else if (LUT && a.compact && p == 0) {
+      } else if (a.compact && p == 0) {
         __syncthreads();  // the small-integer table
       }
 #ifdef FD_FOREST_PROFILE
       if (p < 3) pr_st[1 + 2 * p] = __builtin_amdgcn_s_memtime();
 #endif
-      if (LUT && valid && a.compact) {
+      if (valid && a.compact) {
         switch (q) {
-          case 0: bin_compact_pass<0, kLock, true, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          case 1: bin_compact_pass<1, kLock, true, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          case 2: bin_compact_pass<2, kLock, true, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          default: bin_compact_pass<3, kLock, true, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-        }
-      } else if (valid && a.compact) {
-        switch (q) {
-          case 0: bin_compact_pass<0, kLock, false, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          case 1: bin_compact_pass<1, kLock, false, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          case 2: bin_compact_pass<2, kLock, false, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
-          default: bin_compact_pass<3, kLock, false, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          case 0: bin_compact_pass<0, kLock, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          case 1: bin_compact_pass<1, kLock, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          case 2: bin_compact_pass<2, kLock, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
+          default: bin_compact_pass<3, kLock, DENSE>(a, v, Xs, txn, f0, f1, glob, tl, o0, anynan, accA); break;
         }
       } else if (!DENSE && valid) {
 #pragma unroll
@@ -1063,13 +857,10 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
 #endif
     }
   }
-  if (G > 0 && !early0) {  // chunk 0 (the tables are dead): forest A's first, or B's when A is absent
-    if (DENSE)  // (stride: the first chunk's length)
-      stage_dense(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, bufA + kEnsBuf, nA > 0 ? a.stride[0] : a.stride[1],
-                  kEnsWG / 64, wave);
-    else
-      stage_pieces(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, nA > 0 ? a.stride[0] : a.stride[1], kEnsWG / 64, wave);
-  }
+  // chunk 0 (the tables are dead): forest A's first, or B's when A is absent (dense: stride is its length)
+  if (G > 0 && !early0)
+    stage_pieces<DENSE>(nA > 0 ? a.nodes[0] : a.nodes[1], bufA, nA > 0 ? a.stride[0] : a.stride[1], kEnsWG / 64, wave,
+                        bufA + kEnsBuf);
   if (gg == 0) {
     lds_store<float>(accA + txn * 4, a.base_margin);
     lds_store<double>(accB + txn * 8, 0.0);
@@ -1117,8 +908,8 @@ __global__ void __launch_bounds__(kEnsWG) ensemble_kernel(EnsArgs a) {
         const int h = g + 1, fb = h >= nA ? 1 : 0;
         const uint32_t nb = (g & 1) ? bufA : bufB;
         if (DENSE) {  // forest B's first chunk by the arguments, any other by this chunk's table
-          if (h == nA) stage_dense(a.nodes[1], nb, nb + kEnsBuf, a.stride[1], 4, wave & 3);
-          else stage_dense(a.nodes[fb] + ((size_t)th1 << 10), nb, nb + kEnsBuf, (int)(th2 << 10), 4, wave & 3);
+          if (h == nA) stage_pieces<true>(a.nodes[1], nb, a.stride[1], 4, wave & 3, nb + kEnsBuf);
+          else stage_pieces<true>(a.nodes[fb] + ((size_t)th1 << 10), nb, (int)(th2 << 10), 4, wave & 3, nb + kEnsBuf);
         } else {
           stage_pieces(a.nodes[fb] + (size_t)(fb ? h - nA : h) * a.stride[fb], nb, a.stride[fb], 4, wave & 3);
         }
@@ -1254,476 +1045,21 @@ const void* pick_ensemble(int out, bool wide, int D) {
 }
 
 // the variable-depth instantiations (contracted chunks; blended columns or route records only: compact rows are the
-// pipelined stream's), walk_pack_var's VD: 1 per tree / 2 per wave
+// pipelined stream's), the kernel's VD: 1 per tree / 2 per wave (walk_pack_var), 3 the dense chunk stream
+template <int VD>
+const void* pick_ensemble_var(int out, bool wide) {
+  if (wide)
+    return out == 1 ? (const void*)ensemble_kernel<8, 1, true, true, VD>
+                    : (const void*)ensemble_kernel<8, 0, true, true, VD>;
+  return out == 1 ? (const void*)ensemble_kernel<8, 1, false, true, VD>
+                  : (const void*)ensemble_kernel<8, 0, false, true, VD>;
+}
 const void* pick_ensemble_var(int out, bool wide, int vd) {
-  if (vd == 2) {
-    if (wide) return out == 1 ? (const void*)ensemble_kernel<8, 1, true, true, 2> : (const void*)ensemble_kernel<8, 0, true, true, 2>;
-    return out == 1 ? (const void*)ensemble_kernel<8, 1, false, true, 2> : (const void*)ensemble_kernel<8, 0, false, true, 2>;
-  }
-  if (vd == 3) {
-    if (wide) return out == 1 ? (const void*)ensemble_kernel<8, 1, true, true, 3> : (const void*)ensemble_kernel<8, 0, true, true, 3>;
-    return out == 1 ? (const void*)ensemble_kernel<8, 1, false, true, 3> : (const void*)ensemble_kernel<8, 0, false, true, 3>;
-  }
-  if (wide) return out == 1 ? (const void*)ensemble_kernel<8, 1, true, true, 1> : (const void*)ensemble_kernel<8, 0, true, true, 1>;
-  return out == 1 ? (const void*)ensemble_kernel<8, 1, false, true, 1> : (const void*)ensemble_kernel<8, 0, false, true, 1>;
+  return vd == 2 ? pick_ensemble_var<2>(out, wide)
+                 : vd == 3 ? pick_ensemble_var<3>(out, wide) : pick_ensemble_var<1>(out, wide);
 }
-
-fd_tree_arrays arrays_of(const PackedForest& f) {
-  fd_tree_arrays t{};
-  t.n_trees = f.n_trees;
-  t.tree_offsets = f.t_off.data();
-  t.left = f.t_left.data();
-  t.right = f.t_right.data();
-  t.feature = f.t_feature.data();
-  t.threshold = f.t_threshold.data();
-  t.default_left = f.t_dleft.data();
-  t.leaf_value = f.t_leaf.data();
-  return t;
-}
-
-// Binning passes over the tables (thr, off): consecutive features whose padded tables fit the staging area (bufA +
-// bufB + the tiles), a larger table alone, searched in global memory; each staged pass's image (element g of the
-// pass at word thr_pad(g), 1 KiB pieces) appended to img. The staging area is sized by the padded layout for the dense
-// kernel too: a plan's passes serve both (64-wide rows keep the padded kernels), and the dense kernel's area behind its
-// 11 KiB tile is the larger (133,120 B against 114,688 B wide), so a pass that fits here fits there.
-void plan_passes(const std::vector<float>& thr, const std::vector<int32_t>& off, int nf, bool wide, EnsPassSet& ps,
-                 std::vector<float>& img) {
-  const size_t stage_floats = (2 * (size_t)ens_buf(wide) + 2 * (size_t)kEnsTile) / 4;
-  ps = EnsPassSet{};
-  ps.f.push_back(0);
-  ps.img_off.push_back((int)(img.size() * 4));
-  int f = 0;
-  while (f < nf) {
-    int g = f;
-    while (g < nf && (size_t)(off[g + 1] - off[f]) + (size_t)(off[g + 1] - off[f]) / 32 + 1 <= stage_floats) ++g;
-    const int np = (int)ps.f.size() - 1;
-    FD_REQUIRE(np < kMaxPass, FD_ERR_UNSUPPORTED, "ensemble binning plan too long");
-    if (g == f) {  // one feature's table exceeds the LDS space
-      ps.glob |= 1ull << np;
-      g = f + 1;
-    } else {
-      const int cnt = off[g] - off[f];
-      const size_t words = cnt > 0 ? (size_t)thr_pad(cnt - 1) + 1 : 0;
-      const size_t base = img.size();
-      img.resize(base + (words + 255) / 256 * 256, 0.f);
-      for (int i = 0; i < cnt; ++i) img[base + (size_t)thr_pad(i)] = thr[(size_t)off[f] + i];
-    }
-    ps.f.push_back(g);
-    ps.img_off.push_back((int)(img.size() * 4));
-    f = g;
-  }
-}
-
-// joint repack of forest A (XGBoost, slot sa) and B (IsolationForest, slot sb) into plan P; either slot may be -1
-// (a single forest: the kernel walks only the other one); false when not possible (the per-model path runs)
-// contract (option ensemble_contract; 0 for the single-forest plans, whose rows are 64-wide): also pack nodes_c[]
-bool build_plan(Engine& e, EnsemblePlan& P, int sa, int sb, bool wide, int contract = 0) {
-  P.valid = false;
-  const PackedForest* F[2] = {sa >= 0 ? &e.forests[sa] : nullptr, sb >= 0 ? &e.forests[sb] : nullptr};
-  if (!F[0] && !F[1]) return false;
-  int D = 0, nf = -1;
-  for (const PackedForest* f : F) {
-    if (!f) continue;
-    // (a sparse-only forest — predict_proba kind or deeper than the heaps — has no binned layout: per-model path)
-    if (f->sparse_only || !f->binned || f->t_off.empty() || (nf >= 0 && f->num_feature != nf)) return false;
-    nf = f->num_feature;
-    D = std::max(D, f->depth);
-  }
-  if (D > 8) return false;
-  if (ens_lds(nf, wide) > kLdsBudget) return false;
-  HostPack hp[2];
-  for (int k = 0; k < 2; ++k) {
-    if (!F[k]) continue;
-    hp[k] = pack_forest_host(F[k]->params, arrays_of(*F[k]), D);
-    if (!hp[k].binned || hp[k].depth != D) return false;
-  }
-  // merged per-feature tables
-  std::vector<std::vector<float>> merged(nf);
-  for (int f = 0; f < nf; ++f) {
-    for (int k = 0; k < 2; ++k) {
-      if (!F[k]) continue;
-      const HostPack& h = hp[k];
-      merged[f].insert(merged[f].end(), h.b_thr.begin() + h.b_thr_off[f], h.b_thr.begin() + h.b_thr_off[f + 1]);
-    }
-    std::sort(merged[f].begin(), merged[f].end());
-    merged[f].erase(std::unique(merged[f].begin(), merged[f].end()), merged[f].end());
-    if (merged[f].size() > (size_t)kMaxBins) return false;
-  }
-  std::vector<float> thr;
-  std::vector<int32_t> off(nf + 1, 0);
-  int maxc = 0;
-  for (int f = 0; f < nf; ++f) {
-    thr.insert(thr.end(), merged[f].begin(), merged[f].end());
-    off[f + 1] = (int32_t)thr.size();
-    maxc = std::max(maxc, (int)merged[f].size());
-  }
-  const int NL = 1 << D;
-  const int CH[2] = {wide ? EnsCfg<true>::CHA : EnsCfg<false>::CHA, wide ? EnsCfg<true>::CHB : EnsCfg<false>::CHB};
-  const size_t leaf_sz[2] = {sizeof(float), sizeof(double)};
-  for (int k = 0; k < 2; ++k) {
-    if (!F[k]) {
-      P.n_trees[k] = P.n_chunks[k] = 0;
-      P.CH[k] = CH[k];
-      P.stride[k] = 0;
-      continue;
-    }
-    const HostPack& h = hp[k];
-    const int T = h.n_trees, nc = (T + CH[k] - 1) / CH[k];
-    // chunk: CH node blocks of 1 KiB (walk_ens link addressing), then the CH trees' leaf values [CH][NL];
-    // padding trees (a partial last chunk) keep zero nodes and zero leaves
-    const size_t leaf_bytes = (size_t)CH[k] * NL * leaf_sz[k];
-    const size_t stride = ((size_t)CH[k] * 1024 + leaf_bytes + 1023) / 1024 * 1024;
-    FD_REQUIRE(stride <= ens_buf(wide), FD_ERR_UNSUPPORTED, "ensemble chunk exceeds its LDS buffer");
-    std::vector<char> blob((size_t)nc * stride, 0);
-    for (int i = 0; i < T; ++i) {
-      const char* src = h.b_blob.data() + (size_t)(i / h.b_chunk) * h.b_chunk_stride + (size_t)(i % h.b_chunk) *
-                                                                                          h.b_tree_bytes;
-      char* chunk = blob.data() + (size_t)(i / CH[k]) * stride;
-      uint32_t* dst = reinterpret_cast<uint32_t*>(chunk + (size_t)(i % CH[k]) * 1024);
-      for (int s = 1; s < NL; ++s) {
-        uint32_t w;
-        std::memcpy(&w, src + (size_t)s * 4, 4);
-        const uint32_t f = (w >> 10) & 63u;
-        if (!h.pad[(size_t)i * NL + s]) {  // real split: its threshold's index in the merged table
-          const int j = (int)(w >> 16);
-          const float t = h.b_thr[h.b_thr_off[f] + j];
-          const uint32_t jm = (uint32_t)(std::lower_bound(merged[f].begin(), merged[f].end(), t) - merged[f].begin());
-          w = (jm << 16) | (w & 0xFFFFu);
-        }
-        const uint32_t link = s < (NL >> 1) ? (uint32_t)s : (uint32_t)(s - (NL >> 1));
-        // walk_ens node word: the pair-row of the u16 bin tile in bits [15:10], the feature's half in bit 1
-        dst[s] = (w & 0xFFFF0001u) | ((f >> 1) << 10) | (link << 3) | ((f & 1u) << 1);
-      }
-      std::memcpy(chunk + (size_t)CH[k] * 1024 + (size_t)(i % CH[k]) * NL * leaf_sz[k], src + (size_t)NL * 4,
-                  (size_t)NL * leaf_sz[k]);
-    }
-    P.nodes[k].ensure(blob.size());
-    FD_HIP(hipMemcpy(P.nodes[k].ptr, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    P.n_trees[k] = T;
-    P.CH[k] = CH[k];
-    P.n_chunks[k] = nc;
-    P.stride[k] = stride;
-  }
-  // The contracted forests (contract_forest_host) in the same chunk geometry: tree i a perfect heap of depth dw <= D —
-  // the deepest of its wave's TPG trees (contract 1) or its own depth d_i (contract 2) — in its 1 KiB node block, the
-  // last split level's link s - 2^(dw - 1), dw in heap slot 0 (it arrives with the chunk's DMA), its 2^dw leaves at
-  // the start of its leaf row [2^D]. Padding trees of a partial last chunk: pad nodes and zero leaves (contract 2:
-  // depth 1). Thresholds are looked up in the same merged tables (the contracted trees' are a subset).
-  P.contract = contract;
-  P.contracted = false;
-  P.nodes_pruned = 0;
-  P.steps_full = P.steps_c = 0;
-  P.dense_len0[0] = P.dense_len0[1] = P.dense_chunks[0] = P.dense_chunks[1] = 0;
-  for (int k = 0; k < 2 && contract; ++k) {
-    if (!F[k]) continue;
-    const bool xgb = F[k]->params.kind == FD_FOREST_XGB_BINARY_LOGISTIC;
-    const ContractedForest c = contract_forest_host(F[k]->params, arrays_of(*F[k]));
-    if (contract >= 3) {  // the dense chunk stream (dense_layout_host), walked by the VD 3 kernel
-      FD_REQUIRE(ens_lds_dense(wide) <= ens_lds(kMaxFeatures, wide), FD_ERR_UNSUPPORTED,
-                 "dense layout: more LDS than the padded layout");
-      const DenseLayout L = dense_layout_host(c, xgb, merged, wide, contract, kDenseOwnerBias);
-      P.nodes_c[k].ensure(L.blob.size());
-      FD_HIP(hipMemcpy(P.nodes_c[k].ptr, L.blob.data(), L.blob.size(), hipMemcpyHostToDevice));
-      P.dense_len0[k] = L.chunk_len.empty() ? 0 : L.chunk_len[0];
-      P.dense_chunks[k] = (int)L.chunk_len.size();
-      P.steps_c += L.steps;
-      P.nodes_pruned += c.pruned;
-      continue;
-    }
-    const int T = hp[k].n_trees, nc = P.n_chunks[k], ch = CH[k], tpg = ch / 4;
-    const size_t nb = (size_t)nc * ch;
-    std::vector<int> dw(nb, 1);
-    for (int i = 0; i < T; ++i) dw[i] = std::min(c.depth[i], D);
-    if (contract == 1)
-      for (size_t g0 = 0; g0 < nb; g0 += tpg) {
-        const int mx = *std::max_element(dw.begin() + g0, dw.begin() + g0 + tpg);
-        std::fill(dw.begin() + g0, dw.begin() + g0 + tpg, mx);
-      }
-    std::vector<char> blob((size_t)nc * P.stride[k], 0);
-    std::vector<int32_t> cur(2 * NL);
-    for (size_t i = 0; i < nb; ++i) {
-      char* chunk = blob.data() + (i / ch) * P.stride[k];
-      uint32_t* dst = reinterpret_cast<uint32_t*>(chunk + (i % ch) * 1024);
-      dst[0] = (uint32_t)dw[i];
-      const int nl = 1 << dw[i];
-      if ((int)i >= T) {  // a padding tree: pad nodes with their links (a zero word would link to heap slot 0)
-        for (int s = 1; s < nl; ++s) dst[s] = (s < (nl >> 1) ? (uint32_t)s : (uint32_t)(s - (nl >> 1))) << 3;
-        continue;
-      }
-      P.steps_c += dw[i];
-      const int64_t a = c.off[i];
-      cur[1] = 0;
-      for (int s = 1; s < nl; ++s) {
-        const int32_t o = cur[s];
-        const uint32_t link = s < (nl >> 1) ? (uint32_t)s : (uint32_t)(s - (nl >> 1));
-        if (c.left[a + o] < 0) {  // a leaf above depth dw: pad node, both ways reach it
-          dst[s] = link << 3;
-          cur[2 * s] = cur[2 * s + 1] = o;
-          continue;
-        }
-        const uint32_t f = (uint32_t)c.feature[a + o];
-        const float thr = xgb ? (float)c.threshold[a + o] : sklearn_threshold_to_lt(c.threshold[a + o]);
-        const uint32_t jm = (uint32_t)(std::lower_bound(merged[f].begin(), merged[f].end(), thr) - merged[f].begin());
-        dst[s] = (jm << 16) | ((f >> 1) << 10) | (link << 3) | ((f & 1u) << 1) | (c.dleft[a + o] ? 1u : 0u);
-        cur[2 * s] = c.left[a + o];
-        cur[2 * s + 1] = c.right[a + o];
-      }
-      char* leaves = chunk + (size_t)ch * 1024 + (i % ch) * NL * leaf_sz[k];
-      for (int s = 0; s < nl; ++s) {
-        const double v = c.leaf[a + cur[nl + s]];
-        if (k == 0) {
-          const float vf = (float)v;
-          std::memcpy(leaves + (size_t)s * 4, &vf, 4);
-        } else {
-          std::memcpy(leaves + (size_t)s * 8, &v, 8);
-        }
-      }
-    }
-    P.nodes_c[k].ensure(blob.size());
-    FD_HIP(hipMemcpy(P.nodes_c[k].ptr, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    P.nodes_pruned += c.pruned;
-  }
-  for (int k = 0; k < 2; ++k) P.steps_full += F[k] ? (long long)hp[k].n_trees * D : 0;
-  P.contracted = contract != 0 && P.steps_c < P.steps_full;
-  P.thr.ensure(std::max<size_t>(4, thr.size() * sizeof(float)));
-  if (!thr.empty()) FD_HIP(hipMemcpy(P.thr.ptr, thr.data(), thr.size() * sizeof(float), hipMemcpyHostToDevice));
-  P.h_thr_off = off;
-  // the bins of the compact vector's constant slots (0 or 0.5): #{t <= value} in the feature's merged table
-  P.h_cbin.assign(kMaxFeatures, 0);
-  for (int f = 0; f < nf && f < kMaxFeatures; ++f) {
-    const int src = compact_src(f);
-    if (src >= 0) continue;
-    const float val = src == -2 ? 0.5f : 0.0f;
-    P.h_cbin[f] = (uint16_t)(std::upper_bound(merged[f].begin(), merged[f].end(), val) - merged[f].begin());
-  }
-  {  // the small-integer compact slots: bins of the values 0 .. kLutN - 1
-    std::vector<uint16_t> lut((size_t)kIntSlots * kLutN, 0);
-    for (int k = 0; k < kIntSlots; ++k) {
-      const int f = kCompactSlot[kIntCompact[k]];
-      if (f >= nf) continue;
-      for (int x = 0; x < kLutN; ++x)
-        lut[(size_t)k * kLutN + x] =
-            (uint16_t)(std::upper_bound(merged[f].begin(), merged[f].end(), (float)x) - merged[f].begin());
-    }
-    P.h_lut = lut;
-  }
-  {  // the binning passes and their table images
-    std::vector<float> img;
-    plan_passes(thr, off, nf, wide, P.passes, img);
-    P.img.ensure(std::max<size_t>(1024, img.size() * sizeof(float)));
-    if (!img.empty()) FD_HIP(hipMemcpy(P.img.ptr, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  P.max_feature_thr = maxc;
-  P.slot[0] = sa;
-  P.slot[1] = sb;
-  P.gen[0] = F[0] ? F[0]->gen : 0;
-  P.gen[1] = F[1] ? F[1]->gen : 0;
-  P.n_forests = (F[0] ? 1 : 0) + (F[1] ? 1 : 0);
-  P.D = D;
-  P.nf = nf;
-  P.wide = wide;
-  P.kind[0] = FD_FOREST_XGB_BINARY_LOGISTIC;
-  P.kind[1] = FD_FOREST_SKLEARN_IFOREST;
-  P.base_margin = F[0] ? hp[0].base_margin : 0.f;
-  P.if_offset = F[1] ? F[1]->if_offset : 0.0;
-  P.if_denominator = F[1] ? F[1]->if_denominator : 0.0;
-  P.valid = true;
-  return true;
-}
-
-bool plan_current(const Engine& e, const EnsemblePlan& P, int sa, int sb, bool wide, int contract = 0) {
-  return P.valid && P.wide == wide && P.contract == contract && P.slot[0] == sa && P.slot[1] == sb &&
-         P.gen[0] == (sa >= 0 ? e.forests[sa].gen : 0) && P.gen[1] == (sb >= 0 ? e.forests[sb].gen : 0);
-}
-
-// the chunk layout for this engine: option "ensemble_chunks" 1 wide / 2 compact, 0 (auto) compact once the engine
-// has RCCL communicators (its sharded step's exchanges co-run with the scoring), else wide
-bool want_wide(const Engine& e) { return e.ens_chunks == 1 || (e.ens_chunks == 0 && !e.comm.ready); }
 
 }  // namespace
-
-// The dense chunk stream of one contracted forest (include/fdengine.h fd_dense_layout_host: the layout, the chunk
-// table and the node word): build_plan's chunks under ensemble_contract 3 / 4 and the host export, one function.
-DenseLayout dense_layout_host(const ContractedForest& c, bool xgb, const std::vector<std::vector<float>>& tables,
-                              bool wide, int mode, int owner_bias) {
-  FD_REQUIRE(mode == 3 || mode == 4, FD_ERR_INVALID_ARG, "dense layout: mode 3 or 4");
-  FD_REQUIRE(owner_bias >= 0 && owner_bias <= 64, FD_ERR_INVALID_ARG, "dense layout: owner_bias in [0, 64]");
-  DenseLayout L;
-  const int T = (int)c.off.size() - 1;
-  const int tpg = (xgb ? (wide ? EnsCfg<true>::CHA : EnsCfg<false>::CHA) : (wide ? EnsCfg<true>::CHB : EnsCfg<false>::CHB)) / 4;
-  const size_t lsz = xgb ? 4 : 8;
-  L.tpg = tpg;
-  L.buf = ens_buf(wide);
-  L.tree.assign((size_t)T, fd_dense_tree{});
-  for (int i = 0; i < T; ++i)
-    FD_REQUIRE(c.depth[i] >= 1 && c.depth[i] <= 8, FD_ERR_UNSUPPORTED, "dense layout: a tree deeper than 8 levels");
-  struct Bundle {
-    std::vector<int> trees;  // forest indices, in place order
-    int depth = 1;
-  };
-  // trees [i0, i0 + n) as bundles, and the data bytes they take
-  auto bundle_up = [&](int i0, int n, std::vector<Bundle>& B) {
-    std::vector<int> order(n);
-    for (int k = 0; k < n; ++k) order[k] = i0 + k;
-    if (mode == 4)
-      std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return c.depth[x] > c.depth[y]; });
-    B.clear();
-    size_t bytes = 0;
-    // a partial bundle (the forest's last chunk): in mode 3 the forest's last trees; in mode 4 at the place in the
-    // sorted order where the sum of the walked depths is least (the last such place) — some place is optimal for these
-    // bundle sizes, so mode 4 never walks more levels than mode 3
-    const int nbund = (n + tpg - 1) / tpg, part = n % tpg;
-    int where = nbund - 1;
-    if (mode == 4 && part) {
-      long long best = -1;
-      for (int w = 0; w < nbund; ++w) {
-        long long cost = 0;
-        for (int q = 0, k = 0; q < nbund; ++q) {
-          const int sz = q == w ? part : tpg;
-          cost += (long long)sz * c.depth[order[k]];  // sorted: the bundle's first tree is its deepest
-          k += sz;
-        }
-        if (best < 0 || cost <= best) best = cost, where = w;
-      }
-    }
-    for (int q = 0, k = 0; q < nbund; ++q) {
-      const int sz = (part && q == where) ? part : tpg;
-      Bundle b;
-      b.trees.assign(order.begin() + k, order.begin() + k + sz);
-      k += sz;
-      for (int t : b.trees) b.depth = std::max(b.depth, (int)c.depth[t]);
-      bytes += b.trees.size() * ((4 + lsz) << b.depth);
-      B.push_back(std::move(b));
-    }
-    return bytes;
-  };
-  std::vector<Bundle> B, cand;
-  std::vector<int32_t> cur(2 * 256);
-  int i0 = 0;
-  while (i0 < T) {
-    int n = 0;
-    for (int m = tpg;; m += tpg) {  // grow by a bundle's worth of trees while the caps hold
-      const int me = std::min(m, T - i0);
-      const size_t bytes = bundle_up(i0, me, cand);
-      if ((int)cand.size() > kDenseSMax || bytes > L.buf) break;
-      n = me;
-      B = cand;
-      if (i0 + m >= T) break;
-    }
-    FD_REQUIRE(n > 0, FD_ERR_UNSUPPORTED, "dense layout: one bundle exceeds the chunk buffer");
-    const int nb = (int)B.size(), ci = (int)L.chunk_off.size();
-    // blocks: the node blocks by size (every block aligned to its own size), then the leaf rows in forest order
-    std::vector<int> by_size;
-    std::vector<int> bundle_of(n), place_of(n);
-    for (int b = 0; b < nb; ++b)
-      for (size_t j = 0; j < B[b].trees.size(); ++j) {
-        bundle_of[B[b].trees[j] - i0] = b;
-        place_of[B[b].trees[j] - i0] = (int)j;
-      }
-    for (int k = 0; k < n; ++k) by_size.push_back(k);
-    std::stable_sort(by_size.begin(), by_size.end(),
-                     [&](int x, int y) { return B[bundle_of[x]].depth > B[bundle_of[y]].depth; });
-    size_t at = 0;
-    for (int k : by_size) {
-      L.tree[i0 + k].node_offset = (int32_t)at;
-      at += (size_t)4 << B[bundle_of[k]].depth;
-    }
-    for (int k = 0; k < n; ++k) {
-      L.tree[i0 + k].leaf_offset = (int32_t)at;
-      at += lsz << B[bundle_of[k]].depth;
-    }
-    FD_REQUIRE(at <= L.buf, FD_ERR_UNSUPPORTED, "dense layout: chunk data exceed the buffer");
-    const size_t data = (at + 1023) / 1024 * 1024, base = L.blob.size();
-    L.blob.resize(base + data + 1024, 0);
-    L.chunk_off.push_back((int64_t)base);
-    L.chunk_len.push_back((int32_t)(data + 1024));
-    char* chunk = L.blob.data() + base;
-    // deal the bundles to the tree groups: deepest first, each to the least loaded group
-    std::vector<int> deal(nb);
-    for (int b = 0; b < nb; ++b) deal[b] = b;
-    std::stable_sort(deal.begin(), deal.end(), [&](int x, int y) { return B[x].depth > B[y].depth; });
-    long long load[4] = {(long long)owner_bias * n, 0, 0, 0};  // sixteenths of a level
-    std::vector<int> group_of(nb);
-    std::vector<std::vector<int>> of_group(4);
-    for (int b : deal) {
-      int g = 0;
-      for (int q = 1; q < 4; ++q)
-        if (load[q] < load[g]) g = q;
-      load[g] += 16ll * B[b].depth;
-      group_of[b] = g;
-      of_group[g].push_back(b);
-    }
-    // the trees
-    for (int k = 0; k < n; ++k) {
-      const int i = i0 + k, dw = B[bundle_of[k]].depth, nl = 1 << dw;
-      fd_dense_tree& t = L.tree[i];
-      t.chunk = ci;
-      t.bundle = bundle_of[k];
-      t.group = group_of[bundle_of[k]];
-      t.depth = dw;
-      L.steps += dw;
-      uint32_t* dst = reinterpret_cast<uint32_t*>(chunk + t.node_offset);
-      const int64_t a = c.off[i];
-      cur[1] = 0;
-      for (int s = 1; s < nl; ++s) {
-        const int32_t o = cur[s];
-        const uint32_t link = s < (nl >> 1) ? (uint32_t)s : (uint32_t)(s - (nl >> 1));
-        if (c.left[a + o] < 0) {  // a leaf above depth dw: pad node, both ways reach it
-          dst[s] = link << 3;
-          cur[2 * s] = cur[2 * s + 1] = o;
-          continue;
-        }
-        const int f = c.feature[a + o];
-        FD_REQUIRE(f >= 0 && f < (int)tables.size() && compact_src(f) >= 0, FD_ERR_UNSUPPORTED,
-                   "dense layout: a split on a constant slot");
-        const uint32_t cs = (uint32_t)compact_src(f);
-        const float thr = xgb ? (float)c.threshold[a + o] : sklearn_threshold_to_lt(c.threshold[a + o]);
-        const std::vector<float>& tb = tables[(size_t)f];
-        const uint32_t jm = (uint32_t)(std::lower_bound(tb.begin(), tb.end(), thr) - tb.begin());
-        // (the root of a tree that resolved to one leaf tests slot 0 against 0, which no table need hold: both ways
-        // reach the same value)
-        FD_REQUIRE(jm <= 0xFFFFu, FD_ERR_UNSUPPORTED, "dense layout: threshold index beyond 16 bits");
-        dst[s] = (jm << 16) | ((cs >> 1) << 10) | (link << 3) | ((cs & 1u) << 1) | (c.dleft[a + o] ? 1u : 0u);
-        cur[2 * s] = c.left[a + o];
-        cur[2 * s + 1] = c.right[a + o];
-      }
-      char* leaves = chunk + t.leaf_offset;
-      for (int s = 0; s < nl; ++s) {
-        const double v = c.leaf[a + cur[nl + s]];
-        if (xgb) {
-          const float vf = (float)v;
-          std::memcpy(leaves + (size_t)s * 4, &vf, 4);
-        } else {
-          std::memcpy(leaves + (size_t)s * 8, &v, 8);
-        }
-      }
-    }
-    // the chunk table
-    uint32_t* tab = reinterpret_cast<uint32_t*>(chunk + data);
-    tab[0] = (uint32_t)n | ((uint32_t)nb << 8);
-    if (ci > 0) {  // the previous chunk's table names this one
-      uint32_t* prev = reinterpret_cast<uint32_t*>(L.blob.data() + L.chunk_off[ci - 1] + L.chunk_len[ci - 1] - 1024);
-      prev[1] = (uint32_t)(base >> 10);
-      prev[2] = (uint32_t)((data + 1024) >> 10);
-    }
-    for (int g = 0; g < 4; ++g) {
-      tab[3] |= (uint32_t)of_group[g].size() << (8 * g);
-      for (size_t s = 0; s < of_group[g].size(); ++s) {
-        const int b = of_group[g][s];
-        uint32_t* e = tab + (64 + 128 * g + 16 * s) / 4;
-        e[0] = (uint32_t)B[b].depth | ((uint32_t)b << 8) | ((uint32_t)g << 16);
-        for (int j = 0; j < 6; ++j) {
-          const int t = B[b].trees[(size_t)j < B[b].trees.size() ? j : 0];
-          e[1 + j / 2] |= (uint32_t)L.tree[t].node_offset << (16 * (j & 1));
-        }
-      }
-    }
-    for (int k = 0; k < n; ++k)
-      tab[576 / 4 + k] = (uint32_t)(2048 * bundle_of[k] + place_of[k]) | ((uint32_t)L.tree[i0 + k].leaf_offset << 16);
-    i0 += n;
-  }
-  return L;
-}
 
 #ifdef FD_FOREST_PROFILE
 // n words from the start of the buffers: slot k's profile at word k * 256 * 16 * 16; *next_slot (if given) = the slot
@@ -1775,9 +1111,7 @@ bool select_pair(Engine& e, const fd_blend_params& p, const int32_t* slots, cons
     return false;
   return true;
 }
-}  // namespace
 
-namespace {
 void plan_args(const EnsemblePlan& P, const float* dX, int64_t n, int32_t ld, bool owner_fixed, EnsArgs& a) {
   a.X = dX;
   a.n = n;
@@ -1918,6 +1252,5 @@ bool launch_ensemble_single(Engine& e, int slot, const float* dX, int64_t n, int
   if (ok) ++e.ens_single_total;
   return ok;
 }
-
 
 }  // namespace fd

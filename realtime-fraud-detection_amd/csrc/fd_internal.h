@@ -212,11 +212,12 @@ struct PackedForest {
   std::vector<uint8_t> t_dleft;
 };
 
-// The fused ensemble kernel's joint repack of one XGBoost and/or one IsolationForest (ensemble.hip): both
-// padded to one depth D, node words rewritten against the MERGED per-feature threshold tables, so one bin
+// The fused ensemble kernel's joint repack of one XGBoost and/or one IsolationForest (ensemble_plan.hip build_plan):
+// both padded to one depth D, node words rewritten against the MERGED per-feature threshold tables, so one bin
 // tile serves both forests; chunks of CH[k] node-only trees, leaf values [tree][2^D] per forest.
-// binning passes of one row form (ensemble.hip): pass p covers features [f[p], f[p + 1]); bit p of glob: searched in
-// global memory (a table larger than the staging area); img_off[p] .. img_off[p + 1]: pass p's padded LDS image
+// binning passes of one row form (ensemble_plan.hip plan_passes): pass p covers features [f[p], f[p + 1]); bit p of
+// glob: searched in global memory (a table larger than the staging area); img_off[p] .. img_off[p + 1]: pass p's
+// padded LDS image
 struct EnsPassSet {
   std::vector<int> f, img_off;
   unsigned long long glob = 0;
@@ -234,28 +235,30 @@ struct EnsemblePlan {
   double if_offset = 0.0, if_denominator = 0.0;
   DeviceBuffer nodes[2], thr;  // per forest: chunk blobs (node blocks + leaf values); merged threshold tables
   std::vector<int32_t> h_thr_off;  // merged table offsets (host copy: binning pass plan)
-  std::vector<uint16_t> h_cbin;    // bins of the compact vector's constant slots (ensemble.hip)
-  std::vector<uint16_t> h_lut;     // bins of the small-integer compact slots' values 0..31 (ensemble.hip kIntCompact)
-  DeviceBuffer img;    // every staged binning pass's padded table image (ensemble.hip plan_passes), LDS-DMA source
+  // (ensemble_plan.hip build_plan / plan_passes)
+  std::vector<uint16_t> h_cbin;    // bins of the compact vector's constant slots
+  std::vector<uint16_t> h_lut;     // bins of the small-integer compact slots' values 0..31
+  DeviceBuffer img;    // every staged binning pass's padded table image, LDS-DMA source
   EnsPassSet passes;
   int max_feature_thr = 0;
-  // the forests contracted against the compact vector's constant slots (ensemble.hip contract_forest_host): the same
-  // chunk geometry, tree t a perfect heap of its own depth d_t (heap slot 0 of its node block holds d_t), its 2^d_t
-  // leaves at the start of its leaf row. contract: the mode the plan was built for (option ensemble_contract: 0 none,
-  // 1 every tree padded to the deepest of its wave's trees, 2 every tree its own depth); contracted: some tree is
-  // walked over fewer than D levels (else the launches keep nodes[])
+  // the forests contracted against the compact vector's constant slots (ensemble_plan.hip contract_forest_host): the
+  // same chunk geometry, tree t a perfect heap of its own depth d_t (heap slot 0 of its node block holds d_t), its
+  // 2^d_t leaves at the start of its leaf row. contract: the mode the plan was built for (option ensemble_contract:
+  // 0 none, 1 every tree padded to the deepest of its wave's trees, 2 every tree its own depth); contracted: some tree
+  // is walked over fewer than D levels (else the launches keep nodes[])
   DeviceBuffer nodes_c[2];
   int contract = 0;
   bool contracted = false;
   long long nodes_pruned = 0;           // splits of the loaded forests that the contracted ones no longer hold
   long long steps_full = 0, steps_c = 0;  // node steps per transaction: n_trees x D over both forests / sum of d_t
-  // contract 3 / 4: nodes_c[] hold the dense chunk stream (ensemble.hip dense_layout_host) — chunks of their own
+  // contract 3 / 4: nodes_c[] hold the dense chunk stream (ensemble_plan.hip dense_layout_host) — chunks of their own
   // lengths, each closed by its 1 KiB chunk table; the first chunk's length and the chunk count per forest
   int dense_len0[2] = {0, 0}, dense_chunks[2] = {0, 0};
 };
 
 // A forest with every split on a constant slot of the compact scoring vector (compact_src(f) < 0: the value 0.5 or 0)
-// replaced by the child that value takes — left iff value < threshold in f32, the packer's comparison — ensemble.hip
+// replaced by the child that value takes — left iff value < threshold in f32, the packer's comparison
+// (ensemble_plan.hip contract_forest_host)
 struct ContractedForest {
   std::vector<int64_t> off;
   std::vector<int32_t> left, right, feature, depth;  // depth: per tree, >= 1 (a lone leaf walks one pad level)
@@ -277,7 +280,7 @@ struct ContractedForest {
 };
 ContractedForest contract_forest_host(const fd_forest_params& p, const fd_tree_arrays& t);
 
-// The dense chunk layout of a contracted forest (ensemble.hip dense_layout_host; include/fdengine.h
+// The dense chunk layout of a contracted forest (ensemble_plan.hip dense_layout_host; include/fdengine.h
 // fd_dense_layout_host documents the chunk table and the node word): what ensemble_kernel's VD 3 instantiation walks.
 constexpr int kDenseSMax = 8;  // bundles per chunk at most: the leaf-index tiles are kDenseSMax x 2 KiB, twice
 struct DenseLayout {
@@ -293,6 +296,13 @@ struct DenseLayout {
 // chunk's trees sorted by depth; owner_bias: sixteenths of a level per tree of the chunk charged to tree group 0
 DenseLayout dense_layout_host(const ContractedForest& c, bool xgb, const std::vector<std::vector<float>>& tables,
                               bool wide, int mode, int owner_bias);
+// The planner's part of the fused path (ensemble_plan.hip), called by ensemble.hip's launchers. build_plan: the joint
+// repack of forest A (XGBoost, slot sa) and B (IsolationForest, slot sb; either may be -1) into P, false when not
+// possible; plan_current: P was built for these slots' forests as loaded now; want_wide: the engine's chunk layout.
+struct Engine;
+bool build_plan(Engine& e, EnsemblePlan& P, int sa, int sb, bool wide, int contract = 0);
+bool plan_current(const Engine& e, const EnsemblePlan& P, int sa, int sb, bool wide, int contract = 0);
+bool want_wide(const Engine& e);
 
 // card-hash routing records (route.hip): one transaction (48 B) / one result (24 B)
 struct __attribute__((aligned(16))) RouteRecord {
@@ -999,6 +1009,7 @@ bool launch_ensemble_single(Engine& e, int slot, const float* dX, int64_t n, int
 bool launch_ensemble(Engine& e, const fd_blend_params& p, const int32_t* slots, const uint8_t* present,
                      const float* dX, int64_t n, int32_t ld, double* dMP, double* dfp, double* dconf, uint8_t* ddec,
                      uint8_t* drisk, const RouteRecord* records, ResultRecord* results, int compact = 0);
+// ensemble_plan.hip: the host copy of a loaded forest, which the joint plans are built from
 void forest_loaded(PackedForest& pf, const fd_forest_params& p, const fd_tree_arrays& t);
 // blend.hip
 void launch_blend(Engine& e, const fd_blend_params& p, int64_t n, const double* const* d_probs,

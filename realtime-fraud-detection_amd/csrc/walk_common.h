@@ -56,12 +56,18 @@ __device__ __forceinline__ void stage_chunk(const char* __restrict__ src, char* 
 // LLVM's waitcnt insertion cannot count LDS reads and emits lgkmcnt(0) before every use, which
 // serialises the walk's independent chains. Hidden from the compiler, the DMA must be completed by
 // the caller: dma_wait() (vmcnt(0)) before the barrier that publishes the chunk.
-__device__ __forceinline__ void stage_chunk_asm(const char* __restrict__ src, uint32_t dst, int stride, int nwaves) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int pieces = stride >> 10;
-  for (int p = wave; p < pieces; p += nwaves) {
+// `bytes` (a multiple of 1 KiB) by nparts waves (this one: part), the pieces dealt round-robin (measured: the piece
+// order rotated by workgroup, so that the CUs staging the same tables and chunks at once spread over the L2 channels,
+// changed nothing). TAIL: the last piece goes to `tail` and not behind the others (the ensemble kernel's dense chunks
+// end in a table that has a fixed place behind the buffer's data bytes).
+template <bool TAIL = false>
+__device__ __forceinline__ void stage_pieces(const char* __restrict__ src, uint32_t dst, int bytes, int nparts,
+                                             int part, uint32_t tail = 0u) {
+  const int lane = threadIdx.x & 63;
+  const int pieces = bytes >> 10;
+  for (int p = part; p < pieces; p += nparts) {
     const char* g = src + (p << 10) + lane * 16;
-    const uint32_t m0 = __builtin_amdgcn_readfirstlane(dst + ((uint32_t)p << 10));
+    const uint32_t m0 = __builtin_amdgcn_readfirstlane((!TAIL || p + 1 < pieces) ? dst + ((uint32_t)p << 10) : tail);
     asm volatile(
         "s_mov_b32 m0, %0\n\t"
         "s_nop 0\n\t"
@@ -70,6 +76,10 @@ __device__ __forceinline__ void stage_chunk_asm(const char* __restrict__ src, ui
         : "s"(m0), "v"(g)
         : "memory", "m0");
   }
+}
+// a chunk of stride bytes by all nwaves waves of the workgroup
+__device__ __forceinline__ void stage_chunk_asm(const char* __restrict__ src, uint32_t dst, int stride, int nwaves) {
+  stage_pieces(src, dst, stride, nwaves, (int)(threadIdx.x >> 6));
 }
 __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 

@@ -1,5 +1,5 @@
 """CPU: fd_contract_forest_host, the contraction of a forest against the constant slots of the compact scoring
-vector (include/fdengine.h; csrc/ensemble.hip contract_forest_host). The pipelined stream's compact and split rows
+vector (include/fdengine.h; csrc/ensemble_plan.hip contract_forest_host). The pipelined stream's compact and split rows
 carry 22 varying slots; slots 12, 24, 25, 33 and 34 are always 0.5 and the other 37 always 0, so a split on one of
 them sends every transaction the same way (left iff value < threshold in f32) and the fused kernel walks the forest
 with those splits resolved. Here: hand-built trees at the comparison's edges and synth.xgboost_doc forests, the

@@ -1,6 +1,6 @@
 """CPU: fd_dense_layout_host, the dense chunk layout of a contracted forest that the fused kernel walks on compact and
 split rows under ensemble_contract 3 (bundles of consecutive trees) and 4 (the chunk's trees sorted by depth), in the
-wide and the compact chunk geometry (include/fdengine.h; csrc/ensemble.hip dense_layout_host). The layout's
+wide and the compact chunk geometry (include/fdengine.h; csrc/ensemble_plan.hip dense_layout_host). The layout's
 invariants from the per-tree records and the chunk tables, and every tree's leaf value read from the blob by the
 documented node word against a plain walk of the original forest, on vectors whose constant slots hold their serving
 values."""

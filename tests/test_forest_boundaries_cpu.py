@@ -86,7 +86,7 @@ def test_reference_agrees_and_rows_cover(key):
 
 
 def _plan_passes(counts, stage_floats):
-    """the pass boundaries ensemble.hip's plan_passes chooses for per-feature table sizes `counts`: a pass takes
+    """the pass boundaries ensemble_plan.hip's plan_passes chooses for per-feature table sizes `counts`: a pass takes
     consecutive features while count + count / 32 + 1 <= stage_floats (one pad word per 32 entries); a table that
     does not fit alone is searched in global memory"""
     off = np.concatenate([[0], np.cumsum(counts)])

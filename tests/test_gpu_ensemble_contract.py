@@ -1,7 +1,7 @@
 """The fused kernel's variable-depth walk over forests contracted against the compact vector's constant slots
-(csrc/ensemble.hip contract_forest_host / walk_ens_var; engine option ensemble_contract), with the twin scheme of
-test_gpu_pipeline.py: a pipelined engine scores split rows (and compact 64-B rows) through the contracted chunks, a
-serial twin scores the full 64-wide vectors with score_batch_device over the uncontracted forests — outputs, model
+(csrc/ensemble_plan.hip contract_forest_host, csrc/ensemble.hip walk_ens_var; engine option ensemble_contract),
+with the twin scheme of test_gpu_pipeline.py: a pipelined engine scores split rows (and compact 64-B rows) through
+the contracted chunks, a serial twin scores the full 64-wide vectors with score_batch_device over the uncontracted forests — outputs, model
 probabilities and end state bit-identical at ensemble_contract 1 (each tree to its wave's deepest), 2 (to its own
 depth) and 0, in the wide and the compact chunk layout. Batches of 33,000 and 33,001 rows reach the fused kernel
 (128 tiles of 256 at least; the last tile partial), a 1,000-row batch between them takes the latency path. The twin's

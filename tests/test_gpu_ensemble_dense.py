@@ -1,4 +1,4 @@
-"""The fused kernel over the dense chunk stream of the contracted forests (csrc/ensemble.hip dense_layout_host,
+"""The fused kernel over the dense chunk stream of the contracted forests (csrc/ensemble_plan.hip dense_layout_host,
 walk_dense, owner_sum_dense; engine option ensemble_contract 3: bundles of consecutive trees, 4: the chunk's trees
 sorted by depth), with the twin scheme of test_gpu_ensemble_contract.py at the same sizes: a pipelined engine scores
 split rows and compact 64-B rows through the dense chunks, a serial twin scores the full 64-wide vectors over the
