@@ -257,6 +257,86 @@ int fd_pack_forest_sparse_host(const fd_forest_params* params, const fd_tree_arr
                                int64_t nodes_cap, void* leaf_values, int64_t values_cap, int32_t* leaf_ids,
                                int64_t ids_cap, fd_sparse_info* info);
 
+/* ---------------------------------------------------------------- forest attribution (TreeSHAP) */
+/* Path-dependent TreeSHAP (Lundberg et al. 2018) of a loaded forest's RAW output: the XGBoost margin, the
+   IsolationForest path-length sum, the predict_proba kind's sum of leaf fractions (what fd_forest_predict_* reports
+   as raw). phi[r, f] for f < num_feature is feature f's contribution to row r's raw output, phi[r, num_feature] the
+   bias (the sum over trees of the cover-weighted mean leaf value; XGBoost: plus the f32 base margin, widened), and a
+   row's num_feature + 1 values sum to its raw output. All arithmetic is f64; a split is decided exactly as the walk
+   decides it (f32, go left <=> x < t with sklearn's (double)x <= thr rewritten; a NaN and a column >= ld take the
+   default direction).
+
+   Covers: a split sends cover[child] / cover[node] of the weight to each child. fd_load_forest carries none;
+   fd_forest_set_cover attaches one f64 per node (XGBoost sum_hessian, sklearn weighted_n_node_samples; n_nodes must be
+   the forest's node count) to the forest in `slot`. Every node reachable from a root needs a finite cover > 0
+   (FD_ERR_INVALID_ARG naming tree and node otherwise). fd_load_xgboost_json keeps the file's sum_hessian itself when
+   every reachable node has a usable one. An explain call on a slot without covers fails with FD_ERR_NOT_LOADED. */
+#define FD_SHAP_MAX_PATH 16 /* unique features on one root-to-leaf path */
+#define FD_SHAP_MAX_TOPK 16
+int fd_forest_set_cover(fd_engine* eng, int slot, const double* cover, int64_t n_nodes);
+/* Host-only: the sum_hessian arrays of an XGBoost JSON file, concatenated in fd_xgboost_json_read's node order.
+   cover == NULL: only *n_nodes. FD_ERR_INVALID_ARG when a tree has no sum_hessian or cap is too small. */
+int fd_xgboost_json_read_cover(const char* path, double* cover, int64_t cap, int64_t* n_nodes);
+
+/* Host-only: the path table the kernel streams. One record per leaf, trees in order, a tree's leaves in left-first
+   depth-first order. A path's elements are the UNIQUE features on it in order of first appearance; repeated splits on
+   a feature are merged: the row must lie in [lo, hi) (lo = -inf without a lower bound; has_hi = 0 and hi = +inf
+   without an upper one), nan_follows = every such edge is its node's default direction, z = the product of the edges'
+   cover ratios. pz = the product of a path's z (the share of the training weight that reaches the leaf). A tree whose
+   root is a leaf gives one path of length 0. A path with more than FD_SHAP_MAX_PATH unique features:
+   FD_ERR_UNSUPPORTED naming the tree. Call with NULL buffers for the sizes in *info. */
+typedef struct {
+  int64_t elem_offset; /* first element in the element array */
+  int32_t len;         /* unique features on the path */
+  int32_t tree;
+  double value;        /* leaf value (XGBoost: the f32 weight, widened) */
+  double pz;
+} fd_shap_path;
+typedef struct {
+  int32_t feature;
+  float lo, hi;
+  uint8_t nan_follows;
+  uint8_t has_hi;
+  uint8_t pad[2];
+  double z;
+} fd_shap_elem;
+typedef struct {
+  int64_t n_paths, n_elems;
+  int32_t max_len;  /* longest path (unique features) */
+  int32_t n_chunks; /* the kernel's fixed split of the table: chunk c holds paths [c * chunk_paths, ...) */
+  int64_t chunk_paths;
+  double bias;      /* sum of value * pz in path order (+ the XGBoost base margin) */
+} fd_shap_info;
+int fd_shap_paths_host(const fd_forest_params* params, const fd_tree_arrays* trees, const double* cover,
+                       fd_shap_path* paths, int64_t paths_cap, fd_shap_elem* elems, int64_t elems_cap,
+                       fd_shap_info* info);
+
+/* Host-only reference: recursive TreeSHAP on the trees themselves (Algorithm 2 of the paper), f64, no path table.
+   phi: n x ld_phi, ld_phi >= num_feature + 1; columns past num_feature are left alone. */
+int fd_forest_shap_ref_host(const fd_forest_params* params, const fd_tree_arrays* trees, const double* cover,
+                            const float* X, int64_t n, int32_t ld, double* phi, int32_t ld_phi);
+
+/* The kernel. d_X: n x ld f32 as for fd_forest_predict_device. d_rows == NULL: every row is explained, phi is n x
+   ld_phi (n_rows is ignored); else phi row j explains X row d_rows[j], j < n_rows — the caller of the _device variant
+   guarantees 0 <= d_rows[j] < n (a row outside is written as NaN), the _host variant checks (FD_ERR_INVALID_ARG).
+   ld_phi >= num_feature + 1. A row's values are a function of that row and the forest only: bit-identical whatever
+   n, the row's position, d_rows or the run (per feature the table's chunks are summed path by path, then the chunk
+   sums in chunk order; no atomics). The path table is built on the first call for a slot and dropped on unload /
+   reload; FD_ERR_UNSUPPORTED as fd_shap_paths_host. Counter "forest_shap_launches". */
+int fd_forest_shap_device(fd_engine* eng, int slot, const float* d_X, int64_t n, int32_t ld, const int64_t* d_rows,
+                          int64_t n_rows, double* d_phi, int32_t ld_phi);
+int fd_forest_shap_host(fd_engine* eng, int slot, const float* X, int64_t n, int32_t ld, const int64_t* rows,
+                        int64_t n_rows, double* phi, int32_t ld_phi);
+
+/* Reason codes: per row of phi (n x ld_phi f64) the k <= FD_SHAP_MAX_TOPK largest of columns 0 .. num_feature-1 (the
+   bias column is not a candidate), by |phi| (by_abs != 0) or by signed phi; ties go to the lower column. A value of
+   0.0 (or NaN) is never reported; unused places hold idx = -1, val = 0. idx: n x k i32, val: n x k f64 (the signed
+   value). */
+int fd_shap_topk_device(fd_engine* eng, const double* d_phi, int64_t n, int32_t ld_phi, int32_t num_feature, int32_t k,
+                        int32_t by_abs, int32_t* d_idx, double* d_val);
+int fd_shap_topk_host(fd_engine* eng, const double* phi, int64_t n, int32_t ld_phi, int32_t num_feature, int32_t k,
+                      int32_t by_abs, int32_t* idx, double* val);
+
 /* ---------------------------------------------------------------- blend (a11-a13) */
 /* Replaces _calculate_model_confidence + _combine_predictions + _make_decision +
    _calculate_risk_level (ml/models/ensemble_predictor.py:252-369) for a batch.
@@ -1122,6 +1202,7 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    "ensemble_nodes_pruned" (splits the current plan's contraction removed), "ensemble_node_steps_per_txn" (tree levels
    walked per transaction by the last fused pair launch), "ensemble_dense_chunks" (chunks of that launch over both
    forests when it walked the dense chunk stream, else 0), "forest_sparse_launches" (launches of the sparse-layout forest kernel),
+   "forest_shap_launches" (launches of the TreeSHAP kernel, fd_forest_shap_*),
    "mlp_launches" (launches of the MLP head's kernel), "graph_steps" (fd_graph_step_* calls with n > 0),
    "text_calls" (fd_text_features_device / _host calls with n > 0), "text_nonascii_rows" (rows those calls flagged
    FD_TEXT_NONASCII; reading it waits for the engine stream),

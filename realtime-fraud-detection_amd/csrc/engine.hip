@@ -435,7 +435,9 @@ int fd_engine_destroy(fd_engine* eng) {
     f.b_blob.release();
     f.b_thr.release();
     f.b_thr_off.release();
+    fd::shap_forget(f);
   }
+  e.shap_partial.release();
   e.stage.release();
   e.scratch_probs.release();
   e.feat_vec.release();
@@ -596,6 +598,8 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
   } else if (k == "forest_sparse_launches") {  // launches of forest_sparse_kernel: predict_proba forests, forests
     // deeper than 10 levels, and any forest under option forest_kernel = 11
     *value = (int64_t)e.sparse_total;
+  } else if (k == "forest_shap_launches") {  // launches of shap_kernel (fd_forest_shap_*: one per batch of 4096 rows)
+    *value = (int64_t)e.shap_total;
   } else if (k == "mlp_launches") {  // launches of the MLP head's kernel (fd_mlp_predict_*, FD_SLOT_MLP models)
     *value = (int64_t)e.mlp_total;
   } else if (k == "graph_steps") {  // fd_graph_step_* calls that appended transactions
@@ -840,6 +844,7 @@ int fd_load_forest(fd_engine* eng, int slot, const fd_forest_params* params, con
   fd::PackedForest& pf = slot_of(e, slot);
   FD_HIP(hipStreamSynchronize(e.stream));  // a reload must not race an in-flight predict
   pf.loaded = false;
+  fd::shap_forget(pf);  // covers and path table belong to the forest that leaves
   fd::repack_forest(pf, *params, *trees);
   FD_API_END
 }
@@ -1022,7 +1027,10 @@ int fd_load_xgboost_json(fd_engine* eng, int slot, const char* path) {
   FD_REQUIRE(t.n_trees > 0, FD_ERR_INVALID_ARG, "xgboost json: no trees");
   FD_HIP(hipStreamSynchronize(e.stream));  // a reload must not race an in-flight predict
   pf.loaded = false;
+  fd::shap_forget(pf);
   fd::repack_forest(pf, p, t);
+  // the file's sum_hessian as covers, when every reachable node has a usable one (else the slot has none)
+  if (m.cover.size() == m.left.size() && fd::shap_cover_problem(t, m.cover.data()).empty()) pf.t_cover = m.cover;
   FD_API_END
 }
 
@@ -1071,6 +1079,7 @@ int fd_unload_forest(fd_engine* eng, int slot) {
   for (auto* b : {&pf.split.bins, &pf.split.nan, &pf.split.leaves}) b->release();
   for (auto* b : {&pf.sp.nodes, &pf.sp.leaf_val, &pf.sp.leaf_ids}) b->release();
   pf.sp.gen = 0;
+  fd::shap_forget(pf);
   pf.sparse_only = false;
   pf.binned = false;
   pf.loaded = false;
@@ -1121,6 +1130,152 @@ int fd_forest_predict_host(fd_engine* eng, int slot, const float* X, int64_t n, 
   st.out(dleaf, leaf, (size_t)n * pf.n_trees);
   st.upload();
   fd::launch_forest(e, pf, dX, n, ld, dprob, draw, dleaf);
+  st.download();
+  FD_API_END
+}
+
+// ---------------------------------------------------------------- forest attribution (shap.hip)
+
+static fd_tree_arrays tree_arrays_of(const fd::PackedForest& pf) {
+  fd_tree_arrays t{};
+  t.n_trees = (int32_t)pf.t_off.size() - 1;
+  t.tree_offsets = pf.t_off.data();
+  t.left = pf.t_left.data();
+  t.right = pf.t_right.data();
+  t.feature = pf.t_feature.data();
+  t.threshold = pf.t_threshold.data();
+  t.default_left = pf.t_dleft.data();
+  t.leaf_value = pf.t_leaf.data();
+  return t;
+}
+
+int fd_forest_set_cover(fd_engine* eng, int slot, const double* cover, int64_t n_nodes) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  fd::PackedForest& pf = slot_of(e, slot);
+  FD_REQUIRE(pf.loaded && !pf.t_off.empty(), FD_ERR_NOT_LOADED, "Model in slot " + std::to_string(slot) + " not loaded");
+  FD_REQUIRE(cover != nullptr && n_nodes == pf.t_off.back(), FD_ERR_INVALID_ARG,
+             "cover: one value per node of the forest (" + std::to_string(pf.t_off.back()) + ")");
+  const std::string bad = fd::shap_cover_problem(tree_arrays_of(pf), cover);
+  FD_REQUIRE(bad.empty(), FD_ERR_INVALID_ARG, bad);
+  FD_HIP(hipStreamSynchronize(e.stream));  // an explain call in flight reads the table these covers replace
+  fd::shap_forget(pf);
+  pf.t_cover.assign(cover, cover + n_nodes);
+  FD_API_END
+}
+
+int fd_xgboost_json_read_cover(const char* path, double* cover, int64_t cap, int64_t* n_nodes) {
+  FD_API_BEGIN
+  fd::XgbModel m;
+  fd::read_xgboost_json(path, m);
+  const int64_t M = (int64_t)m.left.size();
+  if (n_nodes) *n_nodes = M;
+  if (cover) {
+    FD_REQUIRE((int64_t)m.cover.size() == M, FD_ERR_INVALID_ARG, "xgboost json: a tree without sum_hessian");
+    FD_REQUIRE(cap >= M, FD_ERR_INVALID_ARG, "cover buffer too small");
+    std::memcpy(cover, m.cover.data(), (size_t)M * 8);
+  }
+  FD_API_END
+}
+
+int fd_shap_paths_host(const fd_forest_params* params, const fd_tree_arrays* trees, const double* cover,
+                       fd_shap_path* paths, int64_t paths_cap, fd_shap_elem* elems, int64_t elems_cap,
+                       fd_shap_info* info) {
+  FD_API_BEGIN
+  FD_REQUIRE(params && trees && info, FD_ERR_INVALID_ARG, "null params/trees/info");
+  const fd::ShapTable tb = fd::shap_paths_host(*params, *trees, cover);
+  *info = tb.info;
+  if (paths) {
+    FD_REQUIRE(paths_cap >= tb.info.n_paths, FD_ERR_INVALID_ARG, "path buffer too small");
+    std::memcpy(paths, tb.paths.data(), tb.paths.size() * sizeof(fd_shap_path));
+  }
+  if (elems) {
+    FD_REQUIRE(elems_cap >= tb.info.n_elems, FD_ERR_INVALID_ARG, "element buffer too small");
+    std::memcpy(elems, tb.elems.data(), tb.elems.size() * sizeof(fd_shap_elem));
+  }
+  FD_API_END
+}
+
+int fd_forest_shap_ref_host(const fd_forest_params* params, const fd_tree_arrays* trees, const double* cover,
+                            const float* X, int64_t n, int32_t ld, double* phi, int32_t ld_phi) {
+  FD_API_BEGIN
+  FD_REQUIRE(params && trees, FD_ERR_INVALID_ARG, "null params/trees");
+  fd::shap_ref_host(*params, *trees, cover, X, n, ld, phi, ld_phi);
+  FD_API_END
+}
+
+int fd_forest_shap_device(fd_engine* eng, int slot, const float* d_X, int64_t n, int32_t ld, const int64_t* d_rows,
+                          int64_t n_rows, double* d_phi, int32_t ld_phi) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  fd::PackedForest& pf = slot_of(e, slot);
+  FD_REQUIRE(pf.loaded, FD_ERR_NOT_LOADED, "Model in slot " + std::to_string(slot) + " not loaded");
+  FD_REQUIRE(n >= 0 && (!d_rows || n_rows >= 0), FD_ERR_INVALID_ARG, "negative n");
+  fd::launch_forest_shap(e, pf, d_X, n, ld, d_rows, n_rows, d_phi, ld_phi);
+  FD_API_END
+}
+
+int fd_forest_shap_host(fd_engine* eng, int slot, const float* X, int64_t n, int32_t ld, const int64_t* rows,
+                        int64_t n_rows, double* phi, int32_t ld_phi) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  fd::PackedForest& pf = slot_of(e, slot);
+  FD_REQUIRE(pf.loaded, FD_ERR_NOT_LOADED, "Model in slot " + std::to_string(slot) + " not loaded");
+  FD_REQUIRE(n >= 0 && ld > 0 && (!rows || n_rows >= 0), FD_ERR_INVALID_ARG, "bad arguments");
+  const int64_t total = rows ? n_rows : n;
+  for (int64_t j = 0; rows && j < n_rows; ++j)
+    FD_REQUIRE(rows[j] >= 0 && rows[j] < n, FD_ERR_INVALID_ARG,
+               "rows[" + std::to_string(j) + "] = " + std::to_string(rows[j]) + " is outside [0, n)");
+  if (total == 0 || n == 0) {  // nothing to stage; the argument and cover checks still run
+    fd::launch_forest_shap(e, pf, nullptr, n, ld, rows, 0, nullptr, ld_phi);
+    return FD_OK;
+  }
+  FD_REQUIRE(X && phi, FD_ERR_INVALID_ARG, "null X / phi");
+  Stage st(e);
+  const float* dX;
+  const int64_t* drows;
+  double* dphi;
+  st.in(dX, X, (size_t)n * ld);
+  st.in(drows, rows, (size_t)(rows ? n_rows : 0));
+  st.out(dphi, phi, (size_t)total * ld_phi);
+  st.upload();
+  if (ld_phi > pf.num_feature + 1)  // the staged rows come back whole: columns past the bias as zeros
+    FD_HIP(hipMemsetAsync(dphi, 0, (size_t)total * ld_phi * sizeof(double), e.stream));
+  fd::launch_forest_shap(e, pf, dX, n, ld, drows, n_rows, dphi, ld_phi);
+  st.download();
+  FD_API_END
+}
+
+int fd_shap_topk_device(fd_engine* eng, const double* d_phi, int64_t n, int32_t ld_phi, int32_t num_feature, int32_t k,
+                        int32_t by_abs, int32_t* d_idx, double* d_val) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  fd::launch_shap_topk(e, d_phi, n, ld_phi, num_feature, k, by_abs != 0, d_idx, d_val);
+  FD_API_END
+}
+
+int fd_shap_topk_host(fd_engine* eng, const double* phi, int64_t n, int32_t ld_phi, int32_t num_feature, int32_t k,
+                      int32_t by_abs, int32_t* idx, double* val) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(n >= 0 && ld_phi > 0 && k >= 1 && k <= FD_SHAP_MAX_TOPK, FD_ERR_INVALID_ARG,
+             "bad arguments (k must be in [1, 16])");
+  if (n == 0) return FD_OK;
+  FD_REQUIRE(phi && idx && val, FD_ERR_INVALID_ARG, "null phi / idx / val");
+  Stage st(e);
+  const double* dphi;
+  int32_t* didx;
+  double* dval;
+  st.in(dphi, phi, (size_t)n * ld_phi);
+  st.out(didx, idx, (size_t)n * k);
+  st.out(dval, val, (size_t)n * k);
+  st.upload();
+  fd::launch_shap_topk(e, dphi, n, ld_phi, num_feature, k, by_abs != 0, didx, dval);
   st.download();
   FD_API_END
 }

@@ -164,6 +164,16 @@ struct SparseImage {
   uint64_t gen = 0;
 };
 
+// The TreeSHAP path table of a forest on the device (shap.hip): built on the first explain call, for the
+// PackedForest::gen it was built for (0 = none)
+struct ShapImage {
+  DeviceBuffer paths, elems;
+  int64_t n_paths = 0, chunk_paths = 0;
+  int n_chunks = 0;
+  double bias = 0.0;
+  uint64_t gen = 0;
+};
+
 // A forest repacked into perfect depth-D trees stored as 1-based heaps (see forest.hip header and
 // DESIGN.md "Forest layout"): per tree 2^D node records {f32 thr, u32 meta} (slot 0 unused; children
 // of slot s are 2s / 2s+1) then 2^D leaf values (f32 XGBoost, f64 Isolation Forest); chunks of
@@ -210,6 +220,10 @@ struct PackedForest {
   std::vector<int32_t> t_left, t_right, t_feature;
   std::vector<double> t_threshold, t_leaf;
   std::vector<uint8_t> t_dleft;
+  // attribution (shap.hip): the covers fd_forest_set_cover / fd_load_xgboost_json attached (empty: none) and the path
+  // table built from them; both go with the forest (shap_forget)
+  std::vector<double> t_cover;
+  mutable ShapImage shap;
 };
 
 // The fused ensemble kernel's joint repack of one XGBoost and/or one IsolationForest (ensemble_plan.hip build_plan):
@@ -713,6 +727,8 @@ struct Engine {
   unsigned long long pipe_iter = 0;
   unsigned long long pipe_iter_total = 0;  // counter "pipelined_batches"
   unsigned long long sparse_total = 0;        // counter "forest_sparse_launches": launches of forest_sparse_kernel
+  unsigned long long shap_total = 0;          // counter "forest_shap_launches": launches of shap_kernel
+  DeviceBuffer shap_partial;                  // shap.hip: per-chunk sums of one row batch, [chunk][column][row]
   unsigned long long ens_single_total = 0;    // counter "ensemble_single_launches": fd_forest_predict batches run by
                                               // the fused kernel over one forest (config 2's timed kernel)
   unsigned long long pipe_split_total = 0;    // counter "pipelined_split_batches": of those, split rows
@@ -995,8 +1011,27 @@ struct XgbModel {
   std::vector<int32_t> left, right, feature;
   std::vector<double> threshold, leaf_value;
   std::vector<uint8_t> default_left;
+  std::vector<double> cover;  // sum_hessian per node; empty when a tree of the file has none
 };
 void read_xgboost_json(const char* path, XgbModel& out);
+// shap.hip: path-dependent TreeSHAP (include/fdengine.h "forest attribution")
+struct ShapTable {
+  std::vector<fd_shap_path> paths;
+  std::vector<fd_shap_elem> elems;
+  fd_shap_info info{};
+};
+// "" when every node reachable from a root has a finite cover > 0, else the message naming the first that has not
+std::string shap_cover_problem(const fd_tree_arrays& t, const double* cover);
+ShapTable shap_paths_host(const fd_forest_params& p, const fd_tree_arrays& t, const double* cover);
+void shap_ref_host(const fd_forest_params& p, const fd_tree_arrays& t, const double* cover, const float* X, int64_t n,
+                   int32_t ld, double* phi, int32_t ld_phi);
+// the forest's covers and path table dropped (unload / reload)
+void shap_forget(PackedForest& pf);
+// device pointers, on e.stream; d_rows may be null (then n_rows = n)
+void launch_forest_shap(Engine& e, const PackedForest& pf, const float* d_X, int64_t n, int32_t ld,
+                        const int64_t* d_rows, int64_t n_rows, double* d_phi, int32_t ld_phi);
+void launch_shap_topk(Engine& e, const double* d_phi, int64_t n, int32_t ld_phi, int32_t nf, int32_t k, bool by_abs,
+                      int32_t* d_idx, double* d_val);
 // ensemble.hip: the fused path when the present models are one XGBoost and/or one IsolationForest in engine
 // slots and the batch is large (false: not applicable, the caller runs the per-model kernels + blend).
 // results != nullptr: write route result records (seq from records[i]) instead of the columns.

@@ -267,6 +267,8 @@ void read_xgboost_json(const char* path, XgbModel& out) {
   out.threshold.clear();
   out.default_left.clear();
   out.leaf_value.clear();
+  out.cover.clear();
+  bool covers = true;  // every tree so far had a sum_hessian array of its size
   for (const JVal& tr : trees.arr) {
     const auto& L = num_array(tr, "left_children");
     const auto& R = num_array(tr, "right_children");
@@ -292,8 +294,12 @@ void read_xgboost_json(const char* path, XgbModel& out) {
       out.default_left.push_back(DL[i] != 0.0 ? 1 : 0);
       out.leaf_value.push_back(leaf ? (double)(float)C[i] : 0.0);  // XGBoost holds node values as f32
     }
+    const JVal* sh = tr.get("sum_hessian");
+    covers = covers && sh && sh->type == JVal::Arr && sh->numeric_array && sh->nums.size() == m;
+    if (covers) out.cover.insert(out.cover.end(), sh->nums.begin(), sh->nums.end());
     out.offsets.push_back((int64_t)out.left.size());
   }
+  if (!covers) out.cover.clear();
 }
 
 }  // namespace fd

@@ -112,6 +112,25 @@ class fd_sparse_info(C.Structure):
     ]
 
 
+FD_SHAP_MAX_PATH = 16
+FD_SHAP_MAX_TOPK = 16
+
+
+class fd_shap_path(C.Structure):
+    _fields_ = [("elem_offset", C.c_int64), ("len", C.c_int32), ("tree", C.c_int32), ("value", C.c_double),
+                ("pz", C.c_double)]
+
+
+class fd_shap_elem(C.Structure):
+    _fields_ = [("feature", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("nan_follows", C.c_uint8),
+                ("has_hi", C.c_uint8), ("pad", C.c_uint8 * 2), ("z", C.c_double)]
+
+
+class fd_shap_info(C.Structure):
+    _fields_ = [("n_paths", C.c_int64), ("n_elems", C.c_int64), ("max_len", C.c_int32), ("n_chunks", C.c_int32),
+                ("chunk_paths", C.c_int64), ("bias", C.c_double)]
+
+
 class fd_state_params(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("window_mode", C.c_int32), ("ring_k", C.c_int32), ("seq_len", C.c_int32)]
 
@@ -485,6 +504,16 @@ SIGNATURES = {
                                              _vp, _i64, _vp, C.POINTER(fd_pack_info)]),
     "fd_pack_forest_sparse_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), _vp, _i64,
                                              _vp, _i64, _vp, _i64, C.POINTER(fd_sparse_info)]),
+    "fd_forest_set_cover": (C.c_int, [_vp, C.c_int, _vp, _i64]),
+    "fd_xgboost_json_read_cover": (C.c_int, [C.c_char_p, _vp, _i64, C.POINTER(_i64)]),
+    "fd_shap_paths_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), _vp, _vp, _i64, _vp,
+                                     _i64, C.POINTER(fd_shap_info)]),
+    "fd_forest_shap_ref_host": (C.c_int, [C.POINTER(fd_forest_params), C.POINTER(fd_tree_arrays), _vp, _vp, _i64,
+                                          _i32, _vp, _i32]),
+    "fd_forest_shap_device": (C.c_int, [_vp, C.c_int, _vp, _i64, _i32, _vp, _i64, _vp, _i32]),
+    "fd_forest_shap_host": (C.c_int, [_vp, C.c_int, _vp, _i64, _i32, _vp, _i64, _vp, _i32]),
+    "fd_shap_topk_device": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "fd_shap_topk_host": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
 }
 
 

@@ -95,6 +95,8 @@ class FraudEngine:
         p, t, keep = fa.c_structs()
         N.call("fd_load_forest", self._h, int(slot), C.byref(p), C.byref(t))
         del keep
+        if fa.cover is not None:
+            self.set_cover(slot, fa.cover)
         nt, d, nf = C.c_int32(), C.c_int32(), C.c_int32()
         N.call("fd_forest_info", self._h, int(slot), C.byref(nt), C.byref(d), C.byref(nf))
         self.forests[slot] = {"kind": fa.kind, "n_trees": nt.value, "depth": d.value, "num_feature": nf.value}
@@ -140,6 +142,64 @@ class FraudEngine:
         N.call("fd_forest_predict_device", self._h, int(slot), C.c_void_p(X_ptr), int(n), int(ld),
                C.c_void_p(prob_ptr), C.c_void_p(raw_ptr) if raw_ptr else None,
                C.c_void_p(leaf_ptr) if leaf_ptr else None)
+
+    # ------------------------------------------------------------------ attribution (TreeSHAP)
+    def set_cover(self, slot: int, cover) -> None:
+        """Attach per-node covers (f64, the loaded forest's node order) to the forest in `slot` (fd_forest_set_cover)."""
+        cover = np.ascontiguousarray(np.asarray(cover, dtype=np.float64))
+        N.call("fd_forest_set_cover", self._h, int(slot), _ptr(cover), cover.size)
+
+    def explain(self, slot: int, X, rows=None, top_k: Optional[int] = None, by_abs: bool = True):
+        """Path-dependent TreeSHAP of the forest's raw output (fd_forest_shap_*). X: [n, ld] numpy, or a torch tensor
+        on this engine's device (f32, contiguous), which is explained in place. rows: explain only these row indices
+        of X, in that order. -> phi f64 [rows, num_feature + 1] (the last column is the bias; a row sums to the raw
+        output), or with top_k (<= 16) -> (phi, idx int32 [rows, top_k], val f64 [rows, top_k]): each row's largest
+        contributions by |phi| (by_abs) or by signed phi, -1 / 0 where fewer are non-zero. Device input gives device
+        tensors back, complete on return (the call waits for the engine's stream)."""
+        if slot not in self.forests:
+            raise ValueError(f"Model in slot {slot} not loaded")
+        F = self.forests[slot]["num_feature"]
+        if top_k is not None and not 1 <= int(top_k) <= N.FD_SHAP_MAX_TOPK:
+            raise ValueError(f"top_k must be in [1, {N.FD_SHAP_MAX_TOPK}]")
+        if type(X).__module__.startswith("torch") and X.is_cuda:
+            return self._explain_device(slot, X, rows, top_k, by_abs, F)
+        X = np.ascontiguousarray(np.asarray(X, dtype=np.float32))
+        if X.ndim == 1:
+            X = X.reshape(1, -1)
+        n, ld = X.shape
+        r = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+        m = n if r is None else r.size
+        phi = np.zeros((m, F + 1), np.float64)
+        N.call("fd_forest_shap_host", self._h, int(slot), _ptr(X), n, ld, _ptr(r), m, _ptr(phi), F + 1)
+        if top_k is None:
+            return phi
+        idx = np.full((m, int(top_k)), -1, np.int32)
+        val = np.zeros((m, int(top_k)), np.float64)
+        N.call("fd_shap_topk_host", self._h, _ptr(phi), m, F + 1, F, int(top_k), 1 if by_abs else 0, _ptr(idx),
+               _ptr(val))
+        return phi, idx, val
+
+    def _explain_device(self, slot, X, rows, top_k, by_abs, F):
+        import torch
+        if X.dtype != torch.float32 or X.dim() != 2 or not X.is_contiguous():
+            raise ValueError("device input: a contiguous 2-d float32 tensor")
+        n, ld = X.shape
+        r = None if rows is None else torch.as_tensor(rows, dtype=torch.int64, device=X.device).reshape(-1).contiguous()
+        m = n if r is None else int(r.numel())
+        phi = torch.zeros((m, F + 1), dtype=torch.float64, device=X.device)
+        torch.cuda.current_stream(X.device).synchronize()  # the inputs are ready before the engine's stream reads them
+        N.call("fd_forest_shap_device", self._h, int(slot), C.c_void_p(X.data_ptr()), n, ld,
+               C.c_void_p(r.data_ptr()) if r is not None and m else None, m, C.c_void_p(phi.data_ptr()), F + 1)
+        if top_k is None:
+            self.sync()
+            return phi
+        idx = torch.full((m, int(top_k)), -1, dtype=torch.int32, device=X.device)
+        val = torch.zeros((m, int(top_k)), dtype=torch.float64, device=X.device)
+        torch.cuda.current_stream(X.device).synchronize()
+        N.call("fd_shap_topk_device", self._h, C.c_void_p(phi.data_ptr()), m, F + 1, F, int(top_k),
+               1 if by_abs else 0, C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()))
+        self.sync()
+        return phi, idx, val
 
     # ------------------------------------------------------------------ card state + features
     _TXN_DTYPES = {"card_key": np.uint64, "ts_ms": np.int64, "amount_cents": np.int64, "merchant": np.int32,
@@ -942,6 +1002,51 @@ def pack_forest_sparse_host(fa: ForestArrays):
            C.c_void_p(vals.ctypes.data), info.n_leaves, C.c_void_p(ids.ctypes.data), info.n_leaves, C.byref(info))
     del keep
     return nodes, vals, ids, info
+
+
+def _cover_of(fa: ForestArrays) -> np.ndarray:
+    if fa.cover is None:
+        raise ValueError("the forest carries no covers (ForestArrays.cover): attribution needs them")
+    return np.ascontiguousarray(fa.cover, dtype=np.float64)
+
+
+def shap_paths_host(fa: ForestArrays):
+    """Host-only: the TreeSHAP path table of a forest (fd_shap_paths_host) -> (paths, elems, fd_shap_info), two
+    numpy record arrays with the fields of fd_shap_path / fd_shap_elem (include/fdengine.h)."""
+    p, t, keep = fa.c_structs()
+    cover = _cover_of(fa)
+    info = N.fd_shap_info()
+    N.call("fd_shap_paths_host", C.byref(p), C.byref(t), _ptr(cover), None, 0, None, 0, C.byref(info))
+    paths = np.zeros(info.n_paths, np.dtype(N.fd_shap_path))
+    elems = np.zeros(info.n_elems, np.dtype(N.fd_shap_elem))
+    N.call("fd_shap_paths_host", C.byref(p), C.byref(t), _ptr(cover), _ptr(paths), info.n_paths, _ptr(elems),
+           info.n_elems, C.byref(info))
+    del keep
+    return paths, elems, info
+
+
+def shap_ref_host(fa: ForestArrays, X: np.ndarray) -> np.ndarray:
+    """Host-only: recursive TreeSHAP on the trees (fd_forest_shap_ref_host) -> phi f64 [n, num_feature + 1]."""
+    p, t, keep = fa.c_structs()
+    cover = _cover_of(fa)
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float32))
+    if X.ndim == 1:
+        X = X.reshape(1, -1)
+    n, ld = X.shape
+    phi = np.zeros((n, fa.num_feature + 1), np.float64)
+    N.call("fd_forest_shap_ref_host", C.byref(p), C.byref(t), _ptr(cover), _ptr(X), n, ld, _ptr(phi),
+           fa.num_feature + 1)
+    del keep
+    return phi
+
+
+def read_xgboost_json_cover_native(path) -> np.ndarray:
+    """Host-only: the sum_hessian arrays of an XGBoost JSON file as the engine's C++ reader keeps them."""
+    nn = C.c_int64()
+    N.call("fd_xgboost_json_read_cover", os.fsencode(str(path)), None, 0, C.byref(nn))
+    cover = np.zeros(nn.value, np.float64)
+    N.call("fd_xgboost_json_read_cover", os.fsencode(str(path)), _ptr(cover), nn.value, C.byref(nn))
+    return cover
 
 
 def read_xgboost_json_native(path) -> ForestArrays:

@@ -61,9 +61,16 @@ def prepare_matrix(features_list: List[Dict[str, Any]]) -> np.ndarray:
 
 
 class EnsemblePredictor:
+    # Rows above this fraud probability get feature contributions when explain_contributions is on: the Flink job's
+    # high-risk filter (FraudDetectionJob.java:66-69, fraudScore > 0.7)
+    CONTRIBUTION_THRESHOLD = 0.7
+    CONTRIBUTION_TOP_K = 10
+
     def __init__(self, model_manager, config):
         self.model_manager = model_manager
         self.config = config
+        # off (the default, and a reference config object without the member): results are exactly as before
+        self.explain_contributions = bool(getattr(config.ensemble, "explain_contributions", False))
         self.strategy = EnsembleStrategy(config.ensemble.strategy)
         self.fraud_threshold = config.ensemble.fraud_threshold
         self.confidence_threshold = config.ensemble.confidence_threshold
@@ -98,8 +105,27 @@ class EnsemblePredictor:
             "explanation": self._generate_explanation(preds, features) if self.enable_explanation else {},
             "ensemble_strategy": self.strategy.value, "processing_time_ms": (time.time() - t0) * 1000,
         }
+        if self.explain_contributions and fp > self.CONTRIBUTION_THRESHOLD:
+            contrib = self._feature_contributions([n for n, _, _ in preds], X, [0])
+            if contrib[0]:
+                result["explanation"]["feature_contributions"] = contrib[0]
         self._cache_prediction(key, result)
         return result
+
+    def _feature_contributions(self, names: List[str], X: np.ndarray, rows: List[int]) -> List[Dict[str, Any]]:
+        """Per row of `rows` (indices into X): {model name: {"bias": b, "top": [[feature slot, contribution], ...]}}
+        for every engine-resident forest among `names` — that model's TreeSHAP in its own raw space (margin, path
+        length, leaf-fraction sum), the CONTRIBUTION_TOP_K largest by magnitude. One explain call per model."""
+        mm = self.model_manager
+        out: List[Dict[str, Any]] = [{} for _ in rows]
+        for name in names:
+            if not 0 <= mm.engine_slot(name) < N.FD_SLOT_LSTM:
+                continue  # not a forest in the engine (the heads and the host stand-ins carry no tree attribution)
+            phi, idx, val = mm.explain(name, X, rows=rows, top_k=self.CONTRIBUTION_TOP_K)
+            for j in range(len(rows)):
+                out[j][name] = {"bias": float(phi[j, -1]),
+                                "top": [[int(i), float(v)] for i, v in zip(idx[j], val[j]) if i >= 0]}
+        return out
 
     async def _model_predictions(self, X: np.ndarray):
         enabled = [n for n in self.config.get_enabled_models() if self.model_manager.is_model_loaded(n)]
@@ -276,6 +302,7 @@ class EnsemblePredictor:
         for i, r in enumerate(rows):
             groups.setdefault(len(r), []).append(i)
         scored = {}
+        contributions: Dict[int, Dict[str, Any]] = {}
         for width, idx in groups.items():
             X = np.stack([rows[i] for i in idx])
             try:
@@ -286,6 +313,14 @@ class EnsemblePredictor:
                 r = None  # no model could score this width: those rows fail below, as predict() would
             for j, i in enumerate(idx):
                 scored[i] = (r, j)
+            if self.explain_contributions and r is not None:
+                # one explain call per forest model over this group's high-risk rows
+                hot = [j for j in range(len(idx)) if float(r["fraud_probability"][j]) > self.CONTRIBUTION_THRESHOLD]
+                if hot:
+                    names = [nm for nm, ok in zip(r["models"], r["present"]) if ok]
+                    for j, c in zip(hot, self._feature_contributions(names, X, hot)):
+                        if c:
+                            contributions[idx[j]] = c
         per_txn_ms = (time.time() - t0) * 1000 / len(features_list)
         out = []
         for i, f in enumerate(features_list):
@@ -306,4 +341,6 @@ class EnsemblePredictor:
                 "explanation": self._generate_explanation(preds, f) if self.enable_explanation else {},
                 "ensemble_strategy": self.strategy.value, "processing_time_ms": per_txn_ms,
             })
+            if i in contributions:
+                out[-1]["explanation"]["feature_contributions"] = contributions[i]
         return out

@@ -42,6 +42,9 @@ class ForestArrays:
     if_offset: float = 0.0
     if_denominator: float = 0.0
     meta: Dict[str, Any] = field(default_factory=dict)
+    # float64, one per node: the weight the tree was grown with at that node (XGBoost sum_hessian, sklearn
+    # weighted_n_node_samples). TreeSHAP splits by cover[child] / cover[node]; None: the model carries none
+    cover: Optional[np.ndarray] = None
 
     @property
     def n_trees(self) -> int:
@@ -83,7 +86,8 @@ def _concat(trees: List[Dict[str, np.ndarray]], kind: int, num_feature: int, **k
     return ForestArrays(kind=kind, num_feature=num_feature, offsets=offsets, left=cat("left", np.int32),
                         right=cat("right", np.int32), feature=cat("feature", np.int32),
                         threshold=cat("threshold", np.float64), default_left=cat("default_left", np.uint8),
-                        leaf_value=cat("leaf_value", np.float64), **kw)
+                        leaf_value=cat("leaf_value", np.float64),
+                        cover=cat("cover", np.float64) if trees and all("cover" in t for t in trees) else None, **kw)
 
 
 # ----------------------------------------------------------------------------------------- XGBoost
@@ -114,14 +118,21 @@ def xgboost_from_json_doc(doc: Dict[str, Any]) -> ForestArrays:
         leaf = left == -1
         cond = np.asarray(tr["split_conditions"], dtype=np.float64)
         feat = np.where(leaf, 0, np.asarray(tr["split_indices"], dtype=np.int64))
+        sh = tr.get("sum_hessian")
+        cover = {} if sh is None or len(sh) != len(left) else {"cover": np.asarray(sh, dtype=np.float64)}
         trees.append(dict(
-            left=np.where(leaf, -1, left), right=np.asarray(tr["right_children"], dtype=np.int64),
+            **cover, left=np.where(leaf, -1, left), right=np.asarray(tr["right_children"], dtype=np.int64),
             feature=feat, threshold=np.where(leaf, 0.0, cond),
             default_left=np.asarray(tr["default_left"], dtype=np.uint8),
             # XGBoost holds node values as f32; JSON prints them round-trip exact
             leaf_value=np.where(leaf, cond.astype(np.float32).astype(np.float64), 0.0)))
-    return _concat(trees, N.FD_FOREST_XGB_BINARY_LOGISTIC, num_feature, base_score=base_score,
-                   meta={"n_trees": len(trees)})
+    fa = _concat(trees, N.FD_FOREST_XGB_BINARY_LOGISTIC, num_feature, base_score=base_score,
+                 meta={"n_trees": len(trees)})
+    # sum_hessian is the cover when it can serve as one (a model grown with min_child_weight = 0 may hold zeros:
+    # such a forest still loads and scores, it only cannot be explained)
+    if fa.cover is not None and not (np.isfinite(fa.cover).all() and (fa.cover > 0).all()):
+        fa.cover = None
+    return fa
 
 
 def load_xgboost_json(path: str) -> ForestArrays:
@@ -154,7 +165,8 @@ def iforest_from_sklearn(model) -> ForestArrays:
               + np.asarray(model._average_path_length_per_tree[i], dtype=np.float64) - 1.0)
         trees.append(dict(left=np.where(leaf, -1, left), right=np.asarray(t.children_right, dtype=np.int64),
                           feature=f, threshold=np.where(leaf, 0.0, np.asarray(t.threshold, dtype=np.float64)),
-                          default_left=dl, leaf_value=np.where(leaf, lv, 0.0)))
+                          default_left=dl, leaf_value=np.where(leaf, lv, 0.0),
+                          cover=np.asarray(t.weighted_n_node_samples, dtype=np.float64)))
     max_samples = getattr(model, "_max_samples", model.max_samples_)
     denom = float(len(model.estimators_) * _average_path_length([max_samples])[0])
     return _concat(trees, N.FD_FOREST_SKLEARN_IFOREST, n_features, if_offset=float(model.offset_),
@@ -199,6 +211,7 @@ def forest_from_sklearn_classifier(model) -> ForestArrays:
         trees.append(dict(left=np.where(leaf, -1, left), right=np.asarray(t.children_right, dtype=np.int64),
                           feature=np.where(leaf, 0, np.asarray(t.feature, dtype=np.int64)),
                           threshold=np.where(leaf, 0.0, np.asarray(t.threshold, dtype=np.float64)),
-                          default_left=dl, leaf_value=np.where(leaf, value[:, 0, 1], 0.0)))
+                          default_left=dl, leaf_value=np.where(leaf, value[:, 0, 1], 0.0),
+                          cover=np.asarray(t.weighted_n_node_samples, dtype=np.float64)))
     return _concat(trees, N.FD_FOREST_SKLEARN_PROBA, int(model.n_features_in_),
                    meta={"n_trees": len(trees), "class": name})

@@ -314,6 +314,18 @@ class ModelManager:
             return FD_SLOT_LSTM
         return m.slot if isinstance(m, EngineForest) else -1
 
+    def explain(self, model_name: str, X, rows=None, top_k: Optional[int] = None, by_abs: bool = True):
+        """Per-feature contributions (path-dependent TreeSHAP) to an engine-resident forest's RAW output — the XGBoost
+        margin, the IsolationForest path-length sum, a forest classifier's sum of leaf fractions — as
+        FraudEngine.explain returns them. Any other model (the LSTM and MLP heads, a host stand-in) raises ValueError."""
+        if model_name not in self.models:
+            raise ValueError(f"Model {model_name} not loaded")
+        m = self.models[model_name]
+        if not isinstance(m, EngineForest):
+            raise ValueError(f"Model {model_name} ({type(m).__name__}) is not an engine-resident forest: "
+                             "contributions are computed for tree models only")
+        return self.engine.explain(m.slot, X, rows=rows, top_k=top_k, by_abs=by_abs)
+
     async def cleanup(self) -> None:
         async with self.model_lock:
             for name, m in list(self.models.items()):

@@ -31,6 +31,8 @@ class EnsembleConfig:
     confidence_threshold: float = 0.7
     fraud_threshold: float = 0.5
     enable_explanation: bool = True
+    # the engine's own: explanation["feature_contributions"] (TreeSHAP of each forest model) for high-risk rows
+    explain_contributions: bool = False
 
 
 # (name, type, relative path, weight) in the reference's registry order (config.py:128-199)
@@ -56,7 +58,8 @@ class ScoringConfig:
             strategy=env("ENSEMBLE_STRATEGY", "weighted_average"),
             confidence_threshold=float(env("CONFIDENCE_THRESHOLD", "0.7")),
             fraud_threshold=float(env("FRAUD_THRESHOLD", "0.5")),
-            enable_explanation=env("ENABLE_EXPLANATION", "true").lower() == "true")
+            enable_explanation=env("ENABLE_EXPLANATION", "true").lower() == "true",
+            explain_contributions=env("EXPLAIN_CONTRIBUTIONS", "false").lower() == "true")
 
     def get_model_config(self, name: str) -> ModelConfig:
         if name not in self.models:
