@@ -332,10 +332,13 @@ def test_image_deterministic_and_corruption_detected(engine, tmp_path):
 
 def test_image_carries_sink_and_ingest_tables(engine, tmp_path):
     """The image also holds the RedisTransactionSink aggregates (resume on the same shard) and the ingest codec's
-    merchant / vocabulary tables: a fresh engine restored from it continues both exactly."""
+    merchant / vocabulary tables: a fresh engine restored from it continues both exactly (the sink on the bars of
+    tests/test_gpu_sink.py `_check`, every field against oracle/sink_ref.py, then through an eviction)."""
     from fdengine._native import FD_AGG_HOURLY, FD_AGG_MERCHANT
     from fdengine.ingest import IngestCodec
     from oracle.sink_ref import SinkOracle
+    from test_gpu_sink import _check as sink_check
+    from test_gpu_sink import _keys as sink_keys
     batches = synth.window_stream(6, 3000, 300, 40, seed=17, batch_span_ms=900_000)
     engine.state_init(1 << 14, 1, 8)
     engine.sink_init(1 << 13, 1 << 15)
@@ -362,13 +365,29 @@ def test_image_carries_sink_and_ingest_tables(engine, tmp_path):
             fresh.sink_update_host(b["key"], b["ts_ms"], b["amount_cents"], b["merchant"], b["is_fraud"],
                                    b["fraud_score"])
             o.run_batch(b)
-        hours = sorted(int(k.split(":")[1]) for k in o.redis if k.startswith("hourly:"))
-        got = fresh.sink_query(FD_AGG_HOURLY, hours)
-        assert [int(x) for x in got["total_count"]] == [o.redis[f"hourly:{h}"]["total_count"] for h in hours]
-        mk = sorted((int(k.split(":")[1]), int(k.split(":")[2])) for k in o.redis if k.startswith("merchant:"))
-        got = fresh.sink_query(FD_AGG_MERCHANT, [h for _, h in mk], [m for m, _ in mk])
+        nh, nd, nm = sink_check(fresh, o)  # every field of every hourly / daily / merchant-hour bucket
+        assert nh >= 2 and nd >= 1 and nm > 50
+        # eviction on the restored tables (tests/test_gpu_sink.py test_sink_eviction): kept counts, a further update
+        hourly, daily, merch = sink_keys(o)
+        cut = hourly[len(hourly) // 2]
+        kept_e, kept_u = fresh.sink_evict_before(cut)
+        new = [k for k in hourly if k >= cut]
+        assert not fresh.sink_query(FD_AGG_HOURLY, [k for k in hourly if k < cut])["found"].any()
+        got = fresh.sink_query(FD_AGG_HOURLY, new)
+        assert got["found"].all()
+        assert [int(x) for x in got["total_count"]] == [o.redis[f"hourly:{k}"]["total_count"] for k in new]
+        keep_m = [(m, h) for m, h in merch if h >= cut]
+        assert kept_e == len(new) + len(keep_m) + len([d for d in daily if d * 24 + 23 >= cut])
+        assert kept_u == sum(o.redis[f"merchant:{m}:{h}"]["unique_user_count"] for m, h in keep_m)
+        last = batches[-1]
+        fresh.sink_update_host(last["key"], last["ts_ms"], last["amount_cents"], last["merchant"], last["is_fraud"],
+                               last["fraud_score"])
+        o.run_batch(last)
+        got = fresh.sink_query(FD_AGG_HOURLY, new)
+        assert [int(x) for x in got["total_count"]] == [o.redis[f"hourly:{k}"]["total_count"] for k in new]
+        got = fresh.sink_query(FD_AGG_MERCHANT, [h for _, h in keep_m], [m for m, _ in keep_m])
         assert [int(x) for x in got["unique_user_count"]] == \
-               [o.redis[f"merchant:{m}:{h}"]["unique_user_count"] for m, h in mk]
+               [o.redis[f"merchant:{m}:{h}"]["unique_user_count"] for m, h in keep_m]
         # the codec tables came with the image (no set_merchants / set_vocab on the fresh engine)
         c2 = IngestCodec.__new__(IngestCodec)
         c2.eng = fresh
