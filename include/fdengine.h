@@ -337,6 +337,98 @@ int fd_shap_topk_device(fd_engine* eng, const double* d_phi, int64_t n, int32_t 
 int fd_shap_topk_host(fd_engine* eng, const double* phi, int64_t n, int32_t ld_phi, int32_t num_feature, int32_t k,
                       int32_t by_abs, int32_t* idx, double* val);
 
+/* ---------------------------------------------------------------- training: histogram GBDT (ModelTrainer) */
+/* Replaces ModelTrainer.train_xgboost_model's fit (ml/training/model_trainer.py:83-96): a depth-wise histogram
+   gradient-boosting fit of a binary:logistic gbtree forest, whose result is an fd_tree_arrays forest that
+   fd_load_forest serves and an XGBoost JSON file can carry. The arithmetic is the engine's own and declared (DESIGN
+   §4.14, csrc/gbdt_row.h); it is not XGBoost's bit for bit (no weighted quantile sketch, fixed-point gradients, a
+   counter-based sample). The device path (_device / _host) and the single-threaded reference (_ref_host) compile the
+   same rule header and return the same bits.
+
+   Cuts: per feature the sorted non-NaN column v (n_f values); candidates v[floor(k n_f / max_bin)], k = 1 ..
+   max_bin - 1, made unique, a candidate equal to v[0] dropped, at most 254 kept (the lowest). bin(x) = #{cuts <= x},
+   NaN -> bin 255; a row goes left at cut j iff x < cut_j iff bin(x) <= j.
+   Gradients: p = sigma(margin) by a deterministic f64 sigmoid (no exp()), g = p - y and h = p (1 - p) rounded to
+   nearest-even multiples of 2^-24 (int32; h at least one quantum); every sum is int64, so a histogram is the same
+   bits for any grid and any arrival order.
+   Sample: row i is in round t's sample iff fmix64(seed ^ mix(t, i)) < subsample * 2^64; colsample_bytree keeps the
+   max(1, floor(c F)) features with the smallest fmix64(seed ^ mix(t, f)), ties to the lower index. Rows outside the
+   sample enter no histogram but are routed and receive the leaf's margin update.
+   Split: per node, kept feature and cut j two candidates (missing right, missing left), gain = GL^2/(HL+lambda) +
+   GR^2/(HR+lambda) - G^2/(H+lambda) in f64 from the exactly converted sums; valid iff HL, HR >= min_child_weight;
+   the best under (gain desc, feature asc, cut asc, missing-right first); split iff gain > 1e-6 and depth < max_depth.
+   Leaf: w = (float)(-G / (H + lambda) * eta); margins add w in f32 in tree order (as fd_forest_predict_*). */
+typedef struct {
+  int32_t n_rounds;  /* trees, 1 .. 65536 */
+  int32_t max_depth; /* 1 .. 10 */
+  int32_t max_bin;   /* 2 .. 256 */
+  int32_t reserved;
+  double eta;
+  double lambda;           /* >= 0 */
+  double min_child_weight; /* >= 0; lambda + min_child_weight > 0 */
+  double subsample;        /* (0, 1] */
+  double colsample_bytree; /* (0, 1] */
+  double base_score;       /* (0, 1): the margin starts at the loader's -logf(1 / base_score - 1) */
+  uint64_t seed;
+} fd_gbdt_params;
+
+/* A grown forest in caller arrays: the fd_tree_arrays members (trees->... are written despite their const, as by
+   fd_xgboost_json_read; nodes in XGBoost's breadth-first depth-wise numbering, threshold = the cut's f32 value,
+   leaf_value = the f32 leaf weight, both widened) and per node sum_hessian (the node's H), loss_changes (the chosen
+   gain, 0 at leaves) and base_weights (-G / (H + lambda) * eta at every node). */
+typedef struct {
+  fd_tree_arrays* trees;
+  double* sum_hessian;
+  double* loss_changes;
+  double* base_weights;
+} fd_gbdt_model;
+
+/* Host-only. X: n x ld f32, F <= 64 model columns. cuts == NULL or offsets == NULL: only *n_cuts (the total).
+   Else offsets[F + 1] and cuts[*n_cuts]: feature f's cuts are cuts[offsets[f] .. offsets[f + 1]), ascending. */
+int fd_gbdt_cuts_host(const float* X, int64_t n, int32_t ld, int32_t F, int32_t max_bin, float* cuts,
+                      int32_t* offsets, int64_t* n_cuts);
+/* The u8 matrix, n x F row-major. _device: device pointers, on the engine's stream; _host: host pointers through the
+   kernel; _ref_host: plain C++. */
+int fd_gbdt_bin_device(fd_engine* eng, const float* d_X, int64_t n, int32_t ld, int32_t F, const float* d_cuts,
+                       const int32_t* d_offsets, uint8_t* d_bins);
+int fd_gbdt_bin_host(fd_engine* eng, const float* X, int64_t n, int32_t ld, int32_t F, const float* cuts,
+                     const int32_t* offsets, uint8_t* bins);
+int fd_gbdt_bin_ref_host(const float* X, int64_t n, int32_t ld, int32_t F, const float* cuts, const int32_t* offsets,
+                         uint8_t* bins);
+/* margins (f32) and labels (0 / 1) -> the fixed-point pairs; _host runs the kernel, _ref_host plain C++ */
+int fd_gbdt_grad_host(fd_engine* eng, const float* margin, const uint8_t* y, int64_t n, int32_t* g, int32_t* h);
+int fd_gbdt_grad_ref_host(const float* margin, const uint8_t* y, int64_t n, int32_t* g, int32_t* h);
+/* One tree from a binned matrix (n x F), int32 (g, h), a row mask (NULL: every row) and a feature mask (bit f of
+   feature_mask: feature f is searched): the integer-in, tree-out seam of the split search. Of params only max_depth,
+   eta, lambda and min_child_weight are read. out's arrays hold 2^(max_depth + 1) - 1 nodes and trees->tree_offsets
+   two entries; *n_nodes receives the tree's size. _device: d_bins, d_g, d_h, d_row_mask are device pointers, the
+   cuts and the outputs host pointers (the call waits for the engine's stream). */
+int fd_gbdt_grow_tree_device(fd_engine* eng, const uint8_t* d_bins, int64_t n, int32_t F, const float* cuts,
+                             const int32_t* offsets, const int32_t* d_g, const int32_t* d_h, const uint8_t* d_row_mask,
+                             uint64_t feature_mask, const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes);
+int fd_gbdt_grow_tree_host(fd_engine* eng, const uint8_t* bins, int64_t n, int32_t F, const float* cuts,
+                           const int32_t* offsets, const int32_t* g, const int32_t* h, const uint8_t* row_mask,
+                           uint64_t feature_mask, const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes);
+int fd_gbdt_grow_tree_ref_host(const uint8_t* bins, int64_t n, int32_t F, const float* cuts, const int32_t* offsets,
+                               const int32_t* g, const int32_t* h, const uint8_t* row_mask, uint64_t feature_mask,
+                               const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes);
+/* The fit: X n x ld f32 (F <= min(ld, 64) model columns), y n labels (0 / 1), n <= 2^28 (FD_ERR_UNSUPPORTED above).
+   Two calls, as fd_xgboost_json_read: with out == NULL *n_nodes receives the node capacity to allocate (n_rounds *
+   (2^(max_depth + 1) - 1)) and nothing runs; with out (arrays of that capacity, tree_offsets n_rounds + 1) the forest
+   is grown and *n_nodes receives its size. margins (n f32, may be NULL): the final margins, exactly what
+   fd_forest_predict_* reports as raw for the rows of X under the returned forest. _device: d_X, d_y and d_margins
+   are device pointers, out host arrays. The fit loop issues launches only: no copy or wait per level or tree; the
+   trees come back in one copy at the end. FD_ERR_INVALID_ARG: F outside 1..64, max_bin outside 2..256, max_depth
+   outside 1..10, a label other than 0 / 1 (_host and _ref_host check; _device trusts the caller), subsample or
+   colsample_bytree outside (0, 1], the other limits of fd_gbdt_params. Counters "gbdt_hist_launches", "gbdt_trees",
+   "gbdt_nodes_split". Option "gbdt_hist_rows": rows per workgroup of the histogram kernel (results identical). */
+int fd_gbdt_fit_device(fd_engine* eng, const float* d_X, const uint8_t* d_y, int64_t n, int32_t ld, int32_t F,
+                       const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes, float* d_margins);
+int fd_gbdt_fit_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F,
+                     const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes, float* margins);
+int fd_gbdt_fit_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F,
+                         const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes, float* margins);
+
 /* ---------------------------------------------------------------- blend (a11-a13) */
 /* Replaces _calculate_model_confidence + _combine_predictions + _make_decision +
    _calculate_risk_level (ml/models/ensemble_predictor.py:252-369) for a batch.
@@ -1203,6 +1295,8 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    walked per transaction by the last fused pair launch), "ensemble_dense_chunks" (chunks of that launch over both
    forests when it walked the dense chunk stream, else 0), "forest_sparse_launches" (launches of the sparse-layout forest kernel),
    "forest_shap_launches" (launches of the TreeSHAP kernel, fd_forest_shap_*),
+   "gbdt_hist_launches" (launches of the GBDT fit's histogram kernel: one per tree level), "gbdt_trees" (trees grown
+   on the device by fd_gbdt_fit_* / fd_gbdt_grow_tree_*), "gbdt_nodes_split" (split nodes of those trees),
    "mlp_launches" (launches of the MLP head's kernel), "graph_steps" (fd_graph_step_* calls with n > 0),
    "text_calls" (fd_text_features_device / _host calls with n > 0), "text_nonascii_rows" (rows those calls flagged
    FD_TEXT_NONASCII; reading it waits for the engine stream),

@@ -438,6 +438,7 @@ int fd_engine_destroy(fd_engine* eng) {
     fd::shap_forget(f);
   }
   e.shap_partial.release();
+  fd::gbdt_release(e);
   e.stage.release();
   e.scratch_probs.release();
   e.feat_vec.release();
@@ -600,6 +601,12 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
     *value = (int64_t)e.sparse_total;
   } else if (k == "forest_shap_launches") {  // launches of shap_kernel (fd_forest_shap_*: one per batch of 4096 rows)
     *value = (int64_t)e.shap_total;
+  } else if (k == "gbdt_hist_launches") {  // launches of gbdt_hist_kernel (one per tree level with rows)
+    *value = (int64_t)e.gbdt.hist_launches;
+  } else if (k == "gbdt_trees") {  // trees grown on the device (fd_gbdt_fit_* / fd_gbdt_grow_tree_device / _host)
+    *value = (int64_t)e.gbdt.trees;
+  } else if (k == "gbdt_nodes_split") {  // split nodes of those trees
+    *value = (int64_t)e.gbdt.nodes_split;
   } else if (k == "mlp_launches") {  // launches of the MLP head's kernel (fd_mlp_predict_*, FD_SLOT_MLP models)
     *value = (int64_t)e.mlp_total;
   } else if (k == "graph_steps") {  // fd_graph_step_* calls that appended transactions
@@ -779,6 +786,10 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value) {
   } else if (k == "seq_ring_lstm") {  // latency batches: 1 (default) the LSTM reads card histories from the ring
     FD_REQUIRE(value == 0 || value == 1, FD_ERR_INVALID_ARG, "seq_ring_lstm must be 0 or 1");
     e.seq_ring_lstm = value != 0;
+  } else if (k == "gbdt_hist_rows") {  // gbdt.hip: rows a workgroup of the histogram kernel takes (the grid follows);
+    // the sums are integers, so every value gives the same trees
+    FD_REQUIRE(value >= 64 && value <= (1 << 20), FD_ERR_INVALID_ARG, "gbdt_hist_rows must be in 64..1048576");
+    e.gbdt.hist_rows = (int)value;
   } else if (k == "lstm_rows") {  // LSTM tile: 0 auto (4 below 4096 transactions, else 16), 4 or 16
     FD_REQUIRE(value == 0 || value == 4 || value == 16, FD_ERR_INVALID_ARG, "lstm_rows must be 0, 4 or 16");
     e.lstm_rows = (int)value;
@@ -1276,6 +1287,205 @@ int fd_shap_topk_host(fd_engine* eng, const double* phi, int64_t n, int32_t ld_p
   st.out(dval, val, (size_t)n * k);
   st.upload();
   fd::launch_shap_topk(e, dphi, n, ld_phi, num_feature, k, by_abs != 0, didx, dval);
+  st.download();
+  FD_API_END
+}
+
+// ---------------------------------------------------------------- training: histogram GBDT (gbdt.hip)
+
+int fd_gbdt_cuts_host(const float* X, int64_t n, int32_t ld, int32_t F, int32_t max_bin, float* cuts,
+                      int32_t* offsets, int64_t* n_cuts) {
+  FD_API_BEGIN
+  std::vector<float> c;
+  std::vector<int32_t> o;
+  const int64_t total = fd::gbdt_cuts_host(X, n, ld, F, max_bin, c, o, 16);
+  if (n_cuts) *n_cuts = total;
+  if (cuts && offsets) {
+    std::memcpy(offsets, o.data(), o.size() * sizeof(int32_t));
+    if (total) std::memcpy(cuts, c.data(), (size_t)total * sizeof(float));
+  }
+  FD_API_END
+}
+
+int fd_gbdt_bin_ref_host(const float* X, int64_t n, int32_t ld, int32_t F, const float* cuts, const int32_t* offsets,
+                         uint8_t* bins) {
+  FD_API_BEGIN
+  FD_REQUIRE(F >= 1 && F <= 64 && ld >= F && n >= 0 && offsets, FD_ERR_INVALID_ARG, "gbdt: bad arguments");
+  FD_REQUIRE(n == 0 || (X && bins), FD_ERR_INVALID_ARG, "gbdt: null X / bins");
+  fd::gbdt_bin_ref_host(X, n, ld, F, cuts, offsets, bins);
+  FD_API_END
+}
+
+int fd_gbdt_bin_device(fd_engine* eng, const float* d_X, int64_t n, int32_t ld, int32_t F, const float* d_cuts,
+                       const int32_t* d_offsets, uint8_t* d_bins) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  fd::launch_gbdt_bin(e, d_X, n, ld, F, d_cuts, d_offsets, d_bins);
+  FD_API_END
+}
+
+int fd_gbdt_bin_host(fd_engine* eng, const float* X, int64_t n, int32_t ld, int32_t F, const float* cuts,
+                     const int32_t* offsets, uint8_t* bins) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(F >= 1 && F <= 64 && ld >= F && n >= 0 && offsets && offsets[0] == 0, FD_ERR_INVALID_ARG,
+             "gbdt: bad arguments");
+  for (int f = 0; f < F; ++f)
+    FD_REQUIRE(offsets[f + 1] >= offsets[f], FD_ERR_INVALID_ARG, "gbdt: decreasing cut offsets");
+  if (n == 0) return FD_OK;
+  FD_REQUIRE(X && bins, FD_ERR_INVALID_ARG, "gbdt: null X / bins");
+  const float none = 0.0f;
+  const size_t nc = (size_t)offsets[F];
+  Stage st(e);
+  const float *dX, *dcuts;
+  const int32_t* doff;
+  uint8_t* dbins;
+  st.in(dX, X, (size_t)n * ld);
+  st.in(dcuts, nc ? cuts : &none, std::max<size_t>(nc, 1));
+  st.in(doff, offsets, (size_t)F + 1);
+  st.out(dbins, bins, (size_t)n * F);
+  st.upload();
+  fd::launch_gbdt_bin(e, dX, n, ld, F, dcuts, doff, dbins);
+  st.download();
+  FD_API_END
+}
+
+int fd_gbdt_grad_ref_host(const float* margin, const uint8_t* y, int64_t n, int32_t* g, int32_t* h) {
+  FD_API_BEGIN
+  FD_REQUIRE(n >= 0 && (n == 0 || (margin && y && g && h)), FD_ERR_INVALID_ARG, "gbdt: null margin / y / g / h");
+  for (int64_t i = 0; i < n; ++i) FD_REQUIRE(y[i] <= 1, FD_ERR_INVALID_ARG, "gbdt: labels must be 0 or 1");
+  fd::gbdt_grad_ref_host(margin, y, n, g, h);
+  FD_API_END
+}
+
+int fd_gbdt_grad_host(fd_engine* eng, const float* margin, const uint8_t* y, int64_t n, int32_t* g, int32_t* h) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(n >= 0 && (n == 0 || (margin && y && g && h)), FD_ERR_INVALID_ARG, "gbdt: null margin / y / g / h");
+  for (int64_t i = 0; i < n; ++i) FD_REQUIRE(y[i] <= 1, FD_ERR_INVALID_ARG, "gbdt: labels must be 0 or 1");
+  if (n == 0) return FD_OK;
+  Stage st(e);
+  const float* dm;
+  const uint8_t* dy;
+  int32_t *dg, *dh;
+  st.in(dm, margin, (size_t)n);
+  st.in(dy, y, (size_t)n);
+  st.out(dg, g, (size_t)n);
+  st.out(dh, h, (size_t)n);
+  st.upload();
+  fd::launch_gbdt_grad(e, dm, dy, n, dg, dh);
+  st.download();
+  FD_API_END
+}
+
+int fd_gbdt_grow_tree_ref_host(const uint8_t* bins, int64_t n, int32_t F, const float* cuts, const int32_t* offsets,
+                               const int32_t* g, const int32_t* h, const uint8_t* row_mask, uint64_t feature_mask,
+                               const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes) {
+  FD_API_BEGIN
+  FD_REQUIRE(params && out && offsets && (n == 0 || (bins && g && h)), FD_ERR_INVALID_ARG, "gbdt: null argument");
+  fd::gbdt_grow_tree_ref_host(bins, n, F, cuts, offsets, g, h, row_mask, feature_mask, *params, *out, n_nodes);
+  FD_API_END
+}
+
+int fd_gbdt_grow_tree_device(fd_engine* eng, const uint8_t* d_bins, int64_t n, int32_t F, const float* cuts,
+                             const int32_t* offsets, const int32_t* d_g, const int32_t* d_h, const uint8_t* d_row_mask,
+                             uint64_t feature_mask, const fd_gbdt_params* params, fd_gbdt_model* out,
+                             int64_t* n_nodes) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params && out && offsets && (n == 0 || (d_bins && d_g && d_h)), FD_ERR_INVALID_ARG,
+             "gbdt: null argument");
+  fd::gbdt_grow_tree_device(e, d_bins, n, F, cuts, offsets, d_g, d_h, d_row_mask, feature_mask, *params, *out,
+                            n_nodes);
+  FD_API_END
+}
+
+int fd_gbdt_grow_tree_host(fd_engine* eng, const uint8_t* bins, int64_t n, int32_t F, const float* cuts,
+                           const int32_t* offsets, const int32_t* g, const int32_t* h, const uint8_t* row_mask,
+                           uint64_t feature_mask, const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params && out && offsets && (n == 0 || (bins && g && h)), FD_ERR_INVALID_ARG, "gbdt: null argument");
+  fd::gbdt_check_params(*params, n, F, false);
+  const uint8_t none = 0;
+  const int32_t zero = 0;
+  Stage st(e);
+  const uint8_t *dbins, *dmask;
+  const int32_t *dg, *dh;
+  st.in(dbins, n ? bins : &none, std::max<size_t>((size_t)n * F, 1));
+  st.in(dg, n ? g : &zero, std::max<size_t>((size_t)n, 1));
+  st.in(dh, n ? h : &zero, std::max<size_t>((size_t)n, 1));
+  st.in(dmask, row_mask, (size_t)n);
+  st.upload();
+  fd::gbdt_grow_tree_device(e, dbins, n, F, cuts, offsets, dg, dh, n ? dmask : nullptr, feature_mask, *params, *out,
+                            n_nodes);
+  FD_API_END
+}
+
+static void gbdt_capacity(const fd_gbdt_params& p, int64_t n, int32_t F, int64_t* n_nodes) {
+  fd::gbdt_check_params(p, n, F, true);
+  FD_REQUIRE(n_nodes, FD_ERR_INVALID_ARG, "gbdt: null n_nodes");
+  *n_nodes = (int64_t)p.n_rounds * ((1ll << (p.max_depth + 1)) - 1);
+}
+
+int fd_gbdt_fit_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F,
+                         const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes, float* margins) {
+  FD_API_BEGIN
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "gbdt: null params");
+  if (!out) {
+    gbdt_capacity(*params, n, F, n_nodes);
+    return FD_OK;
+  }
+  FD_REQUIRE(n == 0 || (X && y), FD_ERR_INVALID_ARG, "gbdt: null X / y");
+  fd::gbdt_fit_ref_host(X, y, n, ld, F, *params, *out, n_nodes, margins);
+  FD_API_END
+}
+
+int fd_gbdt_fit_device(fd_engine* eng, const float* d_X, const uint8_t* d_y, int64_t n, int32_t ld, int32_t F,
+                       const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes, float* d_margins) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "gbdt: null params");
+  if (!out) {
+    gbdt_capacity(*params, n, F, n_nodes);
+    return FD_OK;
+  }
+  FD_REQUIRE(n == 0 || (d_X && d_y), FD_ERR_INVALID_ARG, "gbdt: null X / y");
+  fd::gbdt_fit_device(e, d_X, d_y, n, ld, F, *params, *out, n_nodes, d_margins);
+  FD_API_END
+}
+
+int fd_gbdt_fit_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F,
+                     const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes, float* margins) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "gbdt: null params");
+  if (!out) {
+    gbdt_capacity(*params, n, F, n_nodes);
+    return FD_OK;
+  }
+  fd::gbdt_check_params(*params, n, F, true);
+  FD_REQUIRE(n == 0 || (X && y), FD_ERR_INVALID_ARG, "gbdt: null X / y");
+  FD_REQUIRE(ld >= F, FD_ERR_INVALID_ARG, "gbdt: ld < F");
+  for (int64_t i = 0; i < n; ++i) FD_REQUIRE(y[i] <= 1, FD_ERR_INVALID_ARG, "gbdt: labels must be 0 or 1");
+  const float none = 0.0f;
+  const uint8_t zero = 0;
+  Stage st(e);
+  const float* dX;
+  const uint8_t* dy;
+  float* dm;
+  st.in(dX, n ? X : &none, std::max<size_t>((size_t)n * ld, 1));
+  st.in(dy, n ? y : &zero, std::max<size_t>((size_t)n, 1));
+  st.out(dm, margins, (size_t)n);
+  st.upload();
+  fd::gbdt_fit_staged(e, dX, n ? X : &none, dy, n, ld, F, *params, *out, n_nodes, dm);
   st.download();
   FD_API_END
 }

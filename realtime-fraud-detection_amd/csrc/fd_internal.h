@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstddef>
 #include <cstdint>
@@ -162,6 +163,14 @@ struct SparseImage {
   DeviceBuffer nodes, leaf_val, leaf_ids;
   int64_t n_nodes = 0, n_leaves = 0;
   uint64_t gen = 0;
+};
+
+// gbdt.hip: device buffers of a fit (they grow and stay), the histogram kernel's rows per workgroup (option
+// "gbdt_hist_rows") and the counters "gbdt_hist_launches" / "gbdt_trees" / "gbdt_nodes_split"
+struct GbdtScratch {
+  DeviceBuffer bins, gh, mask, pos, margin, hist, nodes, cuts, offsets;
+  int hist_rows = 4096;
+  unsigned long long hist_launches = 0, trees = 0, nodes_split = 0;
 };
 
 // The TreeSHAP path table of a forest on the device (shap.hip): built on the first explain call, for the
@@ -729,6 +738,7 @@ struct Engine {
   unsigned long long sparse_total = 0;        // counter "forest_sparse_launches": launches of forest_sparse_kernel
   unsigned long long shap_total = 0;          // counter "forest_shap_launches": launches of shap_kernel
   DeviceBuffer shap_partial;                  // shap.hip: per-chunk sums of one row batch, [chunk][column][row]
+  GbdtScratch gbdt;                           // gbdt.hip: the fit's device buffers and counters
   unsigned long long ens_single_total = 0;    // counter "ensemble_single_launches": fd_forest_predict batches run by
                                               // the fused kernel over one forest (config 2's timed kernel)
   unsigned long long pipe_split_total = 0;    // counter "pipelined_split_batches": of those, split rows
@@ -1014,6 +1024,38 @@ struct XgbModel {
   std::vector<double> cover;  // sum_hessian per node; empty when a tree of the file has none
 };
 void read_xgboost_json(const char* path, XgbModel& out);
+// learner_model_param.base_score is stored in probability space; the margin it seeds is RegLossObj::ProbToMargin =
+// -logf(1 / base_score - 1) evaluated in f32. The loader (forest.hip) and the fit (gbdt.hip) both start from this one.
+inline float xgb_base_margin(double base_score) {
+  const float bs = (float)base_score;
+  return -logf(1.0f / bs - 1.0f);
+}
+// gbdt.hip: the histogram GBDT fit (include/fdengine.h "training"; the rule is gbdt_row.h). Host pointers unless named
+// d_*; the grown trees are written to `out` in breadth-first numbering.
+// threads: host threads the features are split over (the cuts do not depend on it)
+int64_t gbdt_cuts_host(const float* X, int64_t n, int32_t ld, int32_t F, int32_t max_bin, std::vector<float>& cuts,
+                       std::vector<int32_t>& offsets, int threads = 1);
+void gbdt_check_params(const fd_gbdt_params& p, int64_t n, int32_t F, bool fit);
+void gbdt_bin_ref_host(const float* X, int64_t n, int32_t ld, int32_t F, const float* cuts, const int32_t* offsets,
+                       uint8_t* bins);
+void gbdt_grad_ref_host(const float* margin, const uint8_t* y, int64_t n, int32_t* g, int32_t* h);
+void gbdt_grow_tree_ref_host(const uint8_t* bins, int64_t n, int32_t F, const float* cuts, const int32_t* offsets,
+                             const int32_t* g, const int32_t* h, const uint8_t* row_mask, uint64_t feature_mask,
+                             const fd_gbdt_params& p, const fd_gbdt_model& out, int64_t* n_nodes);
+void gbdt_fit_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F, const fd_gbdt_params& p,
+                       const fd_gbdt_model& out, int64_t* n_nodes, float* margins);
+void launch_gbdt_bin(Engine& e, const float* d_X, int64_t n, int32_t ld, int32_t F, const float* d_cuts,
+                     const int32_t* d_offsets, uint8_t* d_bins);
+void launch_gbdt_grad(Engine& e, const float* d_margin, const uint8_t* d_y, int64_t n, int32_t* d_g, int32_t* d_h);
+void gbdt_grow_tree_device(Engine& e, const uint8_t* d_bins, int64_t n, int32_t F, const float* cuts,
+                           const int32_t* offsets, const int32_t* d_g, const int32_t* d_h, const uint8_t* d_row_mask,
+                           uint64_t feature_mask, const fd_gbdt_params& p, const fd_gbdt_model& out, int64_t* n_nodes);
+void gbdt_fit_device(Engine& e, const float* d_X, const uint8_t* d_y, int64_t n, int32_t ld, int32_t F,
+                     const fd_gbdt_params& p, const fd_gbdt_model& out, int64_t* n_nodes, float* d_margins);
+// the same with the matrix also on the host (h_X: the cuts are computed from it without a copy back)
+void gbdt_fit_staged(Engine& e, const float* d_X, const float* h_X, const uint8_t* d_y, int64_t n, int32_t ld,
+                     int32_t F, const fd_gbdt_params& p, const fd_gbdt_model& out, int64_t* n_nodes, float* d_margins);
+void gbdt_release(Engine& e);
 // shap.hip: path-dependent TreeSHAP (include/fdengine.h "forest attribution")
 struct ShapTable {
   std::vector<fd_shap_path> paths;

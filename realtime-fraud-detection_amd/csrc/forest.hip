@@ -263,10 +263,7 @@ HostPack pack_forest_host(const fd_forest_params& p, const fd_tree_arrays& t, in
   hp.tree_bytes = tree_bytes;
   hp.chunk_stride = chunk_stride;
   if (xgb) {
-    // learner_model_param.base_score is stored in probability space; the margin it seeds is
-    // RegLossObj::ProbToMargin = -logf(1/base_score - 1) evaluated in f32.
-    const float bs = (float)p.base_score;
-    hp.base_margin = -logf(1.0f / bs - 1.0f);
+    hp.base_margin = xgb_base_margin(p.base_score);
   }
   return hp;
 }

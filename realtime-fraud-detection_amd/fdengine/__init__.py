@@ -5,11 +5,14 @@ Host side of libfdengine.so (HIP/gfx950, C-ABI in include/fdengine.h). Importing
 loads the native library and fails loudly if it is missing: there is no CPU fallback.
 """
 from . import _native  # noqa: F401  (loads libfdengine.so or raises ImportError)
-from .engine import (FraudEngine, device_count, pack_forest_host, pack_forest_sparse_host,  # noqa: F401
-                     shap_paths_host, shap_ref_host)
+from .engine import (FraudEngine, device_count, gbdt_cuts_host, gbdt_fit_ref_host,  # noqa: F401
+                     gbdt_grow_tree_ref_host, pack_forest_host, pack_forest_sparse_host, shap_paths_host,
+                     shap_ref_host)
 from .forest import (ForestArrays, UnsupportedModel, forest_from_sklearn_classifier,  # noqa: F401
-                     iforest_from_sklearn, load_isolation_forest_joblib, load_xgboost_json, xgboost_from_json_doc)
+                     iforest_from_sklearn, load_isolation_forest_joblib, load_xgboost_json,
+                     xgboost_doc_from_forest, xgboost_from_json_doc)
 
 __all__ = ["FraudEngine", "ForestArrays", "UnsupportedModel", "device_count", "forest_from_sklearn_classifier",
-           "iforest_from_sklearn", "load_isolation_forest_joblib", "load_xgboost_json", "pack_forest_host",
-           "pack_forest_sparse_host", "shap_paths_host", "shap_ref_host", "xgboost_from_json_doc"]
+           "gbdt_cuts_host", "gbdt_fit_ref_host", "gbdt_grow_tree_ref_host", "iforest_from_sklearn",
+           "load_isolation_forest_joblib", "load_xgboost_json", "pack_forest_host", "pack_forest_sparse_host",
+           "shap_paths_host", "shap_ref_host", "xgboost_doc_from_forest", "xgboost_from_json_doc"]

@@ -131,6 +131,18 @@ class fd_shap_info(C.Structure):
                 ("chunk_paths", C.c_int64), ("bias", C.c_double)]
 
 
+class fd_gbdt_params(C.Structure):
+    _fields_ = [("n_rounds", C.c_int32), ("max_depth", C.c_int32), ("max_bin", C.c_int32), ("reserved", C.c_int32),
+                ("eta", C.c_double), ("lambda_", C.c_double), ("min_child_weight", C.c_double),
+                ("subsample", C.c_double), ("colsample_bytree", C.c_double), ("base_score", C.c_double),
+                ("seed", C.c_uint64)]
+
+
+class fd_gbdt_model(C.Structure):
+    _fields_ = [("trees", C.POINTER(fd_tree_arrays)), ("sum_hessian", C.c_void_p), ("loss_changes", C.c_void_p),
+                ("base_weights", C.c_void_p)]
+
+
 class fd_state_params(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("window_mode", C.c_int32), ("ring_k", C.c_int32), ("seq_len", C.c_int32)]
 
@@ -514,6 +526,24 @@ SIGNATURES = {
     "fd_forest_shap_host": (C.c_int, [_vp, C.c_int, _vp, _i64, _i32, _vp, _i64, _vp, _i32]),
     "fd_shap_topk_device": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "fd_shap_topk_host": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "fd_gbdt_cuts_host": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, C.POINTER(_i64)]),
+    "fd_gbdt_bin_device": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "fd_gbdt_bin_host": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "fd_gbdt_bin_ref_host": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "fd_gbdt_grad_host": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "fd_gbdt_grad_ref_host": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "fd_gbdt_grow_tree_device": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                                           C.POINTER(fd_gbdt_params), C.POINTER(fd_gbdt_model), C.POINTER(_i64)]),
+    "fd_gbdt_grow_tree_host": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                                         C.POINTER(fd_gbdt_params), C.POINTER(fd_gbdt_model), C.POINTER(_i64)]),
+    "fd_gbdt_grow_tree_ref_host": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                                             C.POINTER(fd_gbdt_params), C.POINTER(fd_gbdt_model), C.POINTER(_i64)]),
+    "fd_gbdt_fit_device": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(fd_gbdt_params),
+                                     C.POINTER(fd_gbdt_model), C.POINTER(_i64), _vp]),
+    "fd_gbdt_fit_host": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(fd_gbdt_params),
+                                   C.POINTER(fd_gbdt_model), C.POINTER(_i64), _vp]),
+    "fd_gbdt_fit_ref_host": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.POINTER(fd_gbdt_params),
+                                       C.POINTER(fd_gbdt_model), C.POINTER(_i64), _vp]),
 }
 
 

@@ -201,6 +201,58 @@ class FraudEngine:
         self.sync()
         return phi, idx, val
 
+    # ------------------------------------------------------------------ training (histogram GBDT, gbdt.hip)
+    def fit_gbdt(self, X, y, **params) -> ForestArrays:
+        """Grow a binary:logistic gbtree forest on the engine (fd_gbdt_fit_*; the declared semantics are DESIGN
+        §4.14). X: [n, F <= 64] numpy, or a contiguous f32 torch tensor on this engine's device (then y a uint8 tensor
+        there); y: 0 / 1. params: GBDT_DEFAULTS (n_rounds, max_depth, max_bin, eta, reg_lambda, min_child_weight,
+        subsample, colsample_bytree, base_score, seed). -> ForestArrays ready for load_forest, cover = sum_hessian,
+        meta["sum_hessian" | "loss_changes" | "base_weights"] per node and meta["margins"], the final f32 margins of
+        the rows of X (what predict(..., want_raw=True) reports for them)."""
+        p = gbdt_params(**params)
+        if type(X).__module__.startswith("torch") and X.is_cuda:
+            import torch
+            if X.dtype != torch.float32 or X.dim() != 2 or not X.is_contiguous():
+                raise ValueError("device input: a contiguous 2-d float32 tensor")
+            y = y.to(device=X.device, dtype=torch.uint8).contiguous()
+            n, ld = X.shape
+            cap = C.c_int64()
+            N.call("fd_gbdt_fit_device", self._h, None, None, n, ld, ld, C.byref(p), None, C.byref(cap), None)
+            out = _GbdtOut(p.n_rounds, cap.value)
+            margins = torch.zeros(n, dtype=torch.float32, device=X.device)
+            torch.cuda.current_stream(X.device).synchronize()
+            nn = C.c_int64()
+            N.call("fd_gbdt_fit_device", self._h, C.c_void_p(X.data_ptr()), C.c_void_p(y.data_ptr()), n, ld, ld,
+                   C.byref(p), C.byref(out.model), C.byref(nn), C.c_void_p(margins.data_ptr()))
+            fa = out.forest(nn.value, ld, p.base_score)
+            fa.meta["margins"] = margins
+            return fa
+        X, y = _gbdt_xy(X, y)
+        return _gbdt_fit("fd_gbdt_fit_host", (self._h,), X, y, p)
+
+    def gbdt_bin(self, X, cuts, offsets) -> np.ndarray:
+        """The u8 bin matrix of X under the cuts, by the bin kernel (fd_gbdt_bin_host)."""
+        X = np.ascontiguousarray(np.asarray(X, dtype=np.float32))
+        n, ld = X.shape
+        cuts = np.ascontiguousarray(np.concatenate([np.asarray(cuts, np.float32), np.zeros(1, np.float32)]))
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        bins = np.zeros((n, ld), np.uint8)
+        N.call("fd_gbdt_bin_host", self._h, _ptr(X), n, ld, ld, _ptr(cuts), _ptr(offsets), _ptr(bins))
+        return bins
+
+    def gbdt_grad(self, margin, y):
+        """Margins and labels -> the fixed-point (g, h), by the gradient kernel (fd_gbdt_grad_host)."""
+        margin = np.ascontiguousarray(margin, dtype=np.float32)
+        y = np.ascontiguousarray(y, dtype=np.uint8)
+        g, h = np.zeros(margin.size, np.int32), np.zeros(margin.size, np.int32)
+        N.call("fd_gbdt_grad_host", self._h, _ptr(margin), _ptr(y), margin.size, _ptr(g), _ptr(h))
+        return g, h
+
+    def gbdt_grow_tree(self, bins, cuts, offsets, g, h, row_mask=None, feature_mask=None, **params) -> ForestArrays:
+        """One tree from a binned matrix and fixed-point gradients, by the kernels (fd_gbdt_grow_tree_host)."""
+        return _gbdt_grow("fd_gbdt_grow_tree_host", (self._h,), bins, cuts, offsets, g, h, row_mask, feature_mask,
+                          params)
+
     # ------------------------------------------------------------------ card state + features
     _TXN_DTYPES = {"card_key": np.uint64, "ts_ms": np.int64, "amount_cents": np.int64, "merchant": np.int32,
                    "device_fp": np.uint64, "ip_class": np.uint8, "hour": np.uint8, "weekend": np.uint8}
@@ -1065,6 +1117,144 @@ def read_xgboost_json_native(path) -> ForestArrays:
                        right=keep["right"], feature=keep["feature"], threshold=keep["threshold"],
                        default_left=keep["default_left"], leaf_value=keep["leaf_value"], base_score=p.base_score)
     return out
+
+
+# ------------------------------------------------------------------------------------------- training (gbdt.hip)
+
+GBDT_DEFAULTS = dict(n_rounds=100, max_depth=6, max_bin=256, eta=0.1, reg_lambda=1.0, min_child_weight=1.0,
+                     subsample=1.0, colsample_bytree=1.0, base_score=0.5, seed=0)
+
+
+def gbdt_params(**kw) -> "N.fd_gbdt_params":
+    """fd_gbdt_params from keywords (GBDT_DEFAULTS; XGBClassifier's names n_estimators / learning_rate / random_state
+    are accepted for n_rounds / eta / seed)."""
+    alias = {"n_estimators": "n_rounds", "learning_rate": "eta", "random_state": "seed", "lambda_": "reg_lambda"}
+    v = dict(GBDT_DEFAULTS)
+    for k, x in kw.items():
+        k = alias.get(k, k)
+        if k not in v:
+            raise TypeError(f"unknown GBDT parameter {k!r}")
+        v[k] = x
+    return N.fd_gbdt_params(int(v["n_rounds"]), int(v["max_depth"]), int(v["max_bin"]), 0, float(v["eta"]),
+                            float(v["reg_lambda"]), float(v["min_child_weight"]), float(v["subsample"]),
+                            float(v["colsample_bytree"]), float(v["base_score"]), int(v["seed"]) & (2 ** 64 - 1))
+
+
+class _GbdtOut:
+    """Caller arrays of an fd_gbdt_model with room for `cap` nodes of `n_trees` trees."""
+
+    def __init__(self, n_trees: int, cap: int):
+        self.a = dict(offsets=np.zeros(n_trees + 1, np.int64), left=np.zeros(cap, np.int32),
+                      right=np.zeros(cap, np.int32), feature=np.zeros(cap, np.int32),
+                      threshold=np.zeros(cap, np.float64), default_left=np.zeros(cap, np.uint8),
+                      leaf_value=np.zeros(cap, np.float64), sum_hessian=np.zeros(cap, np.float64),
+                      loss_changes=np.zeros(cap, np.float64), base_weights=np.zeros(cap, np.float64))
+        a = self.a
+
+        def P(x, t):
+            return x.ctypes.data_as(C.POINTER(t))
+
+        self.trees = N.fd_tree_arrays(n_trees, P(a["offsets"], C.c_int64), P(a["left"], C.c_int32),
+                                      P(a["right"], C.c_int32), P(a["feature"], C.c_int32),
+                                      P(a["threshold"], C.c_double), P(a["default_left"], C.c_uint8),
+                                      P(a["leaf_value"], C.c_double))
+        self.model = N.fd_gbdt_model(C.pointer(self.trees), a["sum_hessian"].ctypes.data,
+                                     a["loss_changes"].ctypes.data, a["base_weights"].ctypes.data)
+
+    def forest(self, n_nodes: int, num_feature: int, base_score: float) -> ForestArrays:
+        a = {k: (v if k == "offsets" else v[:n_nodes].copy()) for k, v in self.a.items()}
+        return ForestArrays(kind=N.FD_FOREST_XGB_BINARY_LOGISTIC, num_feature=num_feature, offsets=a["offsets"],
+                            left=a["left"], right=a["right"], feature=a["feature"], threshold=a["threshold"],
+                            default_left=a["default_left"], leaf_value=a["leaf_value"], base_score=base_score,
+                            cover=a["sum_hessian"],
+                            meta={"n_trees": len(a["offsets"]) - 1, "sum_hessian": a["sum_hessian"],
+                                  "loss_changes": a["loss_changes"], "base_weights": a["base_weights"]})
+
+
+def _gbdt_xy(X, y):
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float32))
+    if X.ndim != 2:
+        raise ValueError("X: a 2-d matrix")
+    yy = np.asarray(y)
+    if yy.shape != (X.shape[0],):
+        raise ValueError("y: one label per row of X")
+    if not np.isin(yy, (0, 1)).all():
+        raise ValueError("labels must be 0 or 1")
+    return X, np.ascontiguousarray(yy.astype(np.uint8))
+
+
+def _gbdt_fit(fn: str, head, X, y, p):
+    """The two calls of fd_gbdt_fit_*: the capacity, then the fit -> ForestArrays with .meta['margins']."""
+    n, ld = X.shape
+    cap = C.c_int64()
+    N.call(fn, *head, _ptr(X), _ptr(y), n, ld, ld, C.byref(p), None, C.byref(cap), None)
+    out = _GbdtOut(p.n_rounds, cap.value)
+    margins = np.zeros(n, np.float32)
+    nn = C.c_int64()
+    N.call(fn, *head, _ptr(X), _ptr(y), n, ld, ld, C.byref(p), C.byref(out.model), C.byref(nn), _ptr(margins))
+    fa = out.forest(nn.value, ld, p.base_score)
+    fa.meta["margins"] = margins
+    return fa
+
+
+def gbdt_fit_ref_host(X, y, **params) -> ForestArrays:
+    """Host-only: the single-threaded reference fit (fd_gbdt_fit_ref_host), as FraudEngine.fit_gbdt returns it."""
+    X, y = _gbdt_xy(X, y)
+    return _gbdt_fit("fd_gbdt_fit_ref_host", (), X, y, gbdt_params(**params))
+
+
+def gbdt_cuts_host(X, max_bin: int = 256):
+    """Host-only: the per-feature cuts of a matrix (fd_gbdt_cuts_host) -> (cuts f32, offsets int32 [F + 1])."""
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float32))
+    n, ld = X.shape
+    total = C.c_int64()
+    cuts = np.zeros(max(ld, 1) * 254, np.float32)  # the most a feature can have: no size query, one pass
+    offsets = np.zeros(ld + 1, np.int32)
+    N.call("fd_gbdt_cuts_host", _ptr(X), n, ld, ld, int(max_bin), _ptr(cuts), _ptr(offsets), C.byref(total))
+    return cuts[:total.value], offsets
+
+
+def gbdt_bin_ref_host(X, cuts, offsets) -> np.ndarray:
+    """Host-only: the u8 bin matrix (fd_gbdt_bin_ref_host)."""
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float32))
+    n, ld = X.shape
+    cuts = np.ascontiguousarray(np.concatenate([np.asarray(cuts, np.float32), np.zeros(1, np.float32)]))
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    bins = np.zeros((n, ld), np.uint8)
+    N.call("fd_gbdt_bin_ref_host", _ptr(X), n, ld, ld, _ptr(cuts), _ptr(offsets), _ptr(bins))
+    return bins
+
+
+def gbdt_grad_ref_host(margin, y):
+    """Host-only: margins and labels -> the fixed-point (g, h) (fd_gbdt_grad_ref_host); one quantum is 2^-24."""
+    margin = np.ascontiguousarray(margin, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.uint8)
+    g, h = np.zeros(margin.size, np.int32), np.zeros(margin.size, np.int32)
+    N.call("fd_gbdt_grad_ref_host", _ptr(margin), _ptr(y), margin.size, _ptr(g), _ptr(h))
+    return g, h
+
+
+def _gbdt_grow(fn: str, head, bins, cuts, offsets, g, h, row_mask, feature_mask, params):
+    bins = np.ascontiguousarray(bins, dtype=np.uint8)
+    n, F = bins.shape
+    cuts = np.ascontiguousarray(np.concatenate([np.asarray(cuts, np.float32), np.zeros(1, np.float32)]))
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    g = np.ascontiguousarray(g, dtype=np.int32)
+    h = np.ascontiguousarray(h, dtype=np.int32)
+    rm = None if row_mask is None else np.ascontiguousarray(row_mask, dtype=np.uint8)
+    fm = (2 ** F - 1) if feature_mask is None else int(feature_mask)
+    p = gbdt_params(**params)
+    out = _GbdtOut(1, 2 ** (p.max_depth + 1) - 1)
+    nn = C.c_int64()
+    N.call(fn, *head, _ptr(bins), n, F, _ptr(cuts), _ptr(offsets), _ptr(g), _ptr(h), _ptr(rm), C.c_uint64(fm),
+           C.byref(p), C.byref(out.model), C.byref(nn))
+    return out.forest(nn.value, F, p.base_score)
+
+
+def gbdt_grow_tree_ref_host(bins, cuts, offsets, g, h, row_mask=None, feature_mask=None, **params) -> ForestArrays:
+    """Host-only: one tree from a binned matrix and fixed-point gradients (fd_gbdt_grow_tree_ref_host). feature_mask:
+    an integer whose bit f keeps feature f (None: all)."""
+    return _gbdt_grow("fd_gbdt_grow_tree_ref_host", (), bins, cuts, offsets, g, h, row_mask, feature_mask, params)
 
 
 def shard_of(keys, n_shards: int) -> np.ndarray:

@@ -135,6 +135,75 @@ def xgboost_from_json_doc(doc: Dict[str, Any]) -> ForestArrays:
     return fa
 
 
+def xgboost_doc_from_forest(fa: ForestArrays, sum_hessian=None, loss_changes=None, base_weights=None) -> Dict[str, Any]:
+    """The inverse of xgboost_from_json_doc: a binary:logistic gbtree forest as an XGBoost 2.0.3 JSON document (the
+    schema synth.xgboost_doc writes and XGBClassifier.save_model produces). The per-node arrays default to
+    fa.meta["sum_hessian" | "loss_changes" | "base_weights"] (what FraudEngine.fit_gbdt attaches), then to fa.cover
+    for sum_hessian, then to 1.0 / 0.0 / the leaf value. Every number is written as the shortest decimal that reads
+    back to the same f64, so f32 thresholds and leaf weights survive the file bit for bit."""
+    if fa.kind != N.FD_FOREST_XGB_BINARY_LOGISTIC:
+        raise UnsupportedModel("only a binary:logistic gbtree forest has an XGBoost JSON form")
+    M = int(fa.offsets[-1])
+
+    def per_node(given, key, default):
+        a = given if given is not None else fa.meta.get(key)
+        if a is None:
+            return default
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape != (M,):
+            raise ValueError(f"{key}: one value per node ({M})")
+        return a
+
+    leaf_all = np.asarray(fa.left) == -1
+    sh = per_node(sum_hessian, "sum_hessian", fa.cover if fa.cover is not None else np.ones(M))
+    lc = per_node(loss_changes, "loss_changes", np.zeros(M))
+    bw = per_node(base_weights, "base_weights", np.where(leaf_all, fa.leaf_value, 0.0))
+    trees = []
+    for tid in range(fa.n_trees):
+        s = slice(int(fa.offsets[tid]), int(fa.offsets[tid + 1]))
+        left, right = np.asarray(fa.left[s], np.int64), np.asarray(fa.right[s], np.int64)
+        m = len(left)
+        leaf = left == -1
+        parents = np.full(m, 2147483647, np.int64)
+        idx = np.nonzero(~leaf)[0]
+        parents[left[idx]] = idx
+        parents[right[idx]] = idx
+        cond = np.where(leaf, np.asarray(fa.leaf_value[s], np.float64), np.asarray(fa.threshold[s], np.float64))
+        trees.append({
+            "base_weights": [float(v) for v in bw[s]],
+            "categories": [], "categories_nodes": [], "categories_segments": [], "categories_sizes": [],
+            "default_left": [int(v) for v in np.where(leaf, 0, np.asarray(fa.default_left[s]))], "id": tid,
+            "left_children": [int(v) for v in left],
+            "loss_changes": [float(v) for v in np.where(leaf, 0.0, lc[s])],
+            "parents": [int(v) for v in parents],
+            "right_children": [int(v) for v in np.where(leaf, -1, right)],
+            "split_conditions": [float(v) for v in cond],
+            "split_indices": [int(v) for v in np.where(leaf, 0, np.asarray(fa.feature[s]))],
+            "split_type": [0] * m, "sum_hessian": [float(v) for v in sh[s]],
+            "tree_param": {"num_deleted": "0", "num_feature": str(fa.num_feature), "num_nodes": str(m),
+                           "size_leaf_vector": "1"},
+        })
+    T = fa.n_trees
+    return {
+        "learner": {
+            "attributes": {}, "feature_names": [], "feature_types": [],
+            "gradient_booster": {
+                "model": {
+                    "gbtree_model_param": {"num_parallel_tree": "1", "num_trees": str(T)},
+                    "iteration_indptr": list(range(T + 1)),
+                    "tree_info": [0] * T,
+                    "trees": trees,
+                },
+                "name": "gbtree",
+            },
+            "learner_model_param": {"base_score": f"{float(fa.base_score):E}", "boost_from_average": "1",
+                                    "num_class": "0", "num_feature": str(fa.num_feature), "num_target": "1"},
+            "objective": {"name": "binary:logistic", "reg_loss_param": {"scale_pos_weight": "1"}},
+        },
+        "version": [2, 0, 3],
+    }
+
+
 def load_xgboost_json(path: str) -> ForestArrays:
     with open(path, "r") as f:
         return xgboost_from_json_doc(json.load(f))

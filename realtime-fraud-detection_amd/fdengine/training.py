@@ -1,0 +1,255 @@
+"""Drop-in for the reference's ModelTrainer (ml/training/model_trainer.py): same constructor, attributes, method names,
+result keys and written paths; the XGBoost member is fitted, saved, reloaded and scored on the engine.
+
+What differs, on purpose:
+* train_xgboost_model fits with FraudEngine.fit_gbdt (csrc/gbdt.hip) at the reference's parameters (max_depth 6,
+  learning_rate 0.1, subsample 0.8, colsample_bytree 0.8, 100 estimators, random_state as the seed). The fit's
+  arithmetic is the engine's own declared one: the file it writes is XGBoost 2.0.3 JSON that XGBoost and
+  this engine load, but its trees are not the trees XGBoost would have grown.
+* The synthetic frame has the reference's 33 feature columns, label rule and 5 % fraud rate, drawn vectorised from one
+  numpy.random.Generator: the reference's per-row np.random stream (and so its exact rows) is not reproduced.
+* The stratified 80 / 20 split is this module's own (no sklearn.model_selection needed).
+* auc_score is the Mann-Whitney statistic over midranks of the engine's probabilities (equal to sklearn's
+  roc_auc_score); feature_importance is the normalised mean gain per feature, XGBClassifier's default for gbtree.
+* train_isolation_forest delegates to scikit-learn (the engine serves the result; it does not fit it).
+"""
+from __future__ import annotations
+
+import json
+import logging
+import os
+import time
+from datetime import datetime
+from typing import Any, Dict, Optional, Tuple
+
+import numpy as np
+
+from .forest import ForestArrays, xgboost_doc_from_forest
+
+ID_COLUMNS = ("is_fraud", "transaction_id", "user_id", "merchant_id")
+XGB_PARAMS = dict(max_depth=6, learning_rate=0.1, subsample=0.8, colsample_bytree=0.8, n_estimators=100)
+
+
+def roc_auc_midrank(y_true, score) -> float:
+    """Area under the ROC curve as the Mann-Whitney U statistic over midranks (ties count half). Raises ValueError
+    when only one class is present, as sklearn.metrics.roc_auc_score does."""
+    y = np.asarray(y_true).astype(bool).reshape(-1)
+    s = np.asarray(score, dtype=np.float64).reshape(-1)
+    n1, n0 = int(y.sum()), int((~y).sum())
+    if n1 == 0 or n0 == 0:
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    order = np.argsort(s, kind="stable")
+    ss = s[order]
+    start = np.r_[0, np.nonzero(ss[1:] != ss[:-1])[0] + 1]  # first place of each run of equal scores
+    end = np.r_[start[1:], len(ss)]
+    mid = (start + end + 1) / 2.0  # the mean of the 1-based places start + 1 .. end
+    rank = np.empty(len(ss), np.float64)
+    rank[order] = np.repeat(mid, end - start)
+    return float((rank[y].sum() - n1 * (n1 + 1) / 2.0) / (float(n1) * float(n0)))
+
+
+def gain_importance(fa: ForestArrays) -> np.ndarray:
+    """XGBClassifier.feature_importances_ for gbtree (importance_type "gain"): per feature the mean loss change of
+    its splits, normalised to sum 1 (all zeros when no tree split)."""
+    gain = np.asarray(fa.meta["loss_changes"], np.float64)
+    split = np.asarray(fa.left) != -1
+    tot = np.bincount(np.asarray(fa.feature)[split], weights=gain[split], minlength=fa.num_feature)
+    cnt = np.bincount(np.asarray(fa.feature)[split], minlength=fa.num_feature)
+    mean = np.where(cnt > 0, tot / np.maximum(cnt, 1), 0.0)
+    return mean / mean.sum() if mean.sum() > 0 else mean
+
+
+def stratified_split(y, test_size: float, seed: int):
+    """-> (train indices, test indices): per class, round(test_size * count) shuffled rows go to the test side."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    y = np.asarray(y)
+    test = []
+    for c in np.unique(y):
+        idx = rng.permutation(np.nonzero(y == c)[0])
+        test.append(idx[:int(round(test_size * len(idx)))])
+    test = np.sort(np.concatenate(test))
+    keep = np.ones(len(y), bool)
+    keep[test] = False
+    train = rng.permutation(np.nonzero(keep)[0])
+    return train, rng.permutation(test)
+
+
+class ModelTrainer:
+    """Trains the fraud models; the XGBoost member on the engine."""
+
+    def __init__(self, output_dir: str = "/app/models", engine=None):
+        self.logger = logging.getLogger("model_trainer")
+        self.output_dir = output_dir
+        os.makedirs(output_dir, exist_ok=True)
+        self.test_size = 0.2
+        self.validation_size = 0.1
+        self.random_state = 42
+        self._engine = engine
+        self.logger.info(f"Model trainer initialized with output dir: {output_dir}")
+
+    @property
+    def engine(self):
+        if self._engine is None:
+            from .engine import FraudEngine
+            self._engine = FraudEngine(0)
+        return self._engine
+
+    def prepare_training_data(self, data_path: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray,
+                                                                             np.ndarray]:
+        """-> (X_train, X_test, y_train, y_test) from a CSV (pandas) or the synthetic frame."""
+        if data_path and os.path.exists(data_path):
+            import pandas as pd
+            self.logger.info(f"Loading training data from: {data_path}")
+            df = pd.read_csv(data_path)
+        else:
+            self.logger.info("Generating synthetic training data")
+            df = self._generate_synthetic_data()
+        feature_columns = [c for c in df.columns if c not in ID_COLUMNS]
+        X = df[feature_columns].values
+        y = df["is_fraud"].values
+        tr, te = stratified_split(y, self.test_size, self.random_state)
+        self.logger.info(f"Training data prepared: {len(tr)} train, {len(te)} test samples")
+        return X[tr], X[te], y[tr], y[te]
+
+    def train_xgboost_model(self, X_train: np.ndarray, y_train: np.ndarray, X_test: np.ndarray,
+                            y_test: np.ndarray) -> Dict[str, Any]:
+        self.logger.info("Training XGBoost model...")
+        start_time = time.time()
+        eng = self.engine
+        fa = eng.fit_gbdt(X_train, y_train, random_state=self.random_state, **XGB_PARAMS)
+        model_path = os.path.join(self.output_dir, "xgboost", "fraud_classifier.json")
+        os.makedirs(os.path.dirname(model_path), exist_ok=True)
+        with open(model_path, "w") as f:
+            json.dump(xgboost_doc_from_forest(fa), f)
+        # score the held-out split with the file just written, as the serving side will
+        slot = self._free_slot(eng)
+        eng.load_xgboost_file(slot, model_path)
+        try:
+            y_pred_proba = eng.predict(slot, np.asarray(X_test, dtype=np.float32))
+        finally:
+            eng.unload_forest(slot)
+        auc_score = roc_auc_midrank(y_test, y_pred_proba)
+        training_time = time.time() - start_time
+        results = {
+            "model_type": "xgboost",
+            "model_path": model_path,
+            "auc_score": auc_score,
+            "training_time_seconds": training_time,
+            "feature_importance": dict(zip(range(X_train.shape[1]), gain_importance(fa))),
+        }
+        self.logger.info(f"XGBoost training completed in {training_time:.2f}s, AUC: {auc_score:.4f}")
+        return results
+
+    @staticmethod
+    def _free_slot(eng) -> int:
+        from . import _native as N
+        for s in range(7, -1, -1):
+            if s not in eng.forests and s not in (getattr(N, "FD_SLOT_LSTM", -1), getattr(N, "FD_SLOT_MLP", -1)):
+                return s
+        raise RuntimeError("no free forest slot to score the trained model in")
+
+    def _generate_synthetic_data(self, n_samples: int = 10000):
+        """The reference's 33 feature columns and label rule, one vectorised draw per column."""
+        import pandas as pd
+        rng = np.random.Generator(np.random.PCG64(self.random_state))
+        n = n_samples
+
+        def flag(p):
+            return (rng.random(n) < p).astype(np.int64)
+
+        amount = rng.lognormal(3, 1.5, n)
+        cols = {
+            "transaction_id": [f"tx_{i}" for i in range(n)],
+            "user_id": [f"user_{v}" for v in rng.integers(1, 1000, n)],
+            "merchant_id": [f"merchant_{v}" for v in rng.integers(1, 500, n)],
+            "amount": amount,
+            "amount_log": np.log1p(amount),
+            "amount_percentile": rng.uniform(0, 100, n),
+            "amount_zscore": rng.normal(0, 1, n),
+            "hour_of_day": rng.integers(0, 24, n),
+            "day_of_week": rng.integers(0, 7, n),
+            "is_weekend": flag(0.3),
+            "user_transaction_count_1h": rng.poisson(2, n),
+            "user_transaction_count_24h": rng.poisson(10, n),
+            "user_total_amount_24h": rng.lognormal(5, 1, n),
+            "user_avg_amount": rng.lognormal(3, 1, n),
+            "user_unique_merchants_24h": rng.poisson(3, n),
+            "merchant_transaction_count_1h": rng.poisson(50, n),
+            "merchant_fraud_rate": rng.beta(1, 10, n),
+            "merchant_avg_amount": rng.lognormal(4, 1, n),
+            "merchant_risk_score": rng.beta(2, 8, n),
+            "device_risk_score": rng.beta(1, 9, n),
+            "is_new_device": flag(0.2),
+            "ip_risk_score": rng.beta(1, 9, n),
+            "is_tor_ip": flag(0.01),
+            "is_vpn_ip": flag(0.05),
+            "velocity_score": rng.beta(2, 8, n),
+            "amount_velocity_1h": rng.lognormal(2, 1, n),
+            "transaction_velocity_5m": rng.poisson(1, n),
+            "distance_from_home": rng.exponential(10, n),
+            "location_risk_score": rng.beta(2, 8, n),
+            "country_risk_score": rng.beta(3, 7, n),
+            "timezone_mismatch": flag(0.1),
+            "payment_method_risk": rng.beta(2, 8, n),
+            "card_type_risk": rng.beta(2, 8, n),
+            "is_crypto_merchant": flag(0.05),
+            "is_gift_card_merchant": flag(0.1),
+            "cross_border_transaction": flag(0.2),
+        }
+        score = (cols["merchant_fraud_rate"] * 0.3 + cols["device_risk_score"] * 0.2 + cols["ip_risk_score"] * 0.2
+                 + cols["velocity_score"] * 0.15 + cols["location_risk_score"] * 0.15)
+        score = score + 0.3 * ((cols["is_tor_ip"] == 1) | (cols["is_crypto_merchant"] == 1))
+        score = score + 0.2 * ((cols["is_new_device"] == 1) & (amount > 1000))
+        score = score + 0.1 * ((cols["hour_of_day"] < 6) | (cols["hour_of_day"] > 22))
+        score = np.clip(score + rng.normal(0, 0.1, n), 0, 1)
+        fraud = (score > 0.7).astype(np.int64)
+        # hold the fraud rate at 5 %: flip random rows of the class in excess
+        target = int(n * 0.05)
+        have = int(fraud.sum())
+        if have > target:
+            fraud[rng.choice(np.nonzero(fraud == 1)[0], have - target, replace=False)] = 0
+        elif have < target:
+            fraud[rng.choice(np.nonzero(fraud == 0)[0], target - have, replace=False)] = 1
+        cols["is_fraud"] = fraud
+        df = pd.DataFrame(cols)
+        self.logger.info(f"Generated {len(df)} synthetic transactions with {df['is_fraud'].sum()} fraud cases "
+                         f"({df['is_fraud'].mean():.1%} fraud rate)")
+        return df
+
+    def train_isolation_forest(self, X_train: np.ndarray, y_train: np.ndarray, X_test: np.ndarray,
+                               y_test: np.ndarray) -> Dict[str, Any]:
+        """scikit-learn fits the IsolationForest (ImportError without it); the engine serves the saved model."""
+        import joblib
+        from sklearn.ensemble import IsolationForest
+        self.logger.info("Training Isolation Forest model...")
+        start_time = time.time()
+        model = IsolationForest(contamination=0.05, n_estimators=100, random_state=self.random_state)
+        model.fit(X_train[y_train == 0])  # normal transactions only
+        auc_score = roc_auc_midrank(y_test, -model.decision_function(X_test))  # lower scores are more anomalous
+        model_path = os.path.join(self.output_dir, "sklearn", "isolation_forest.joblib")
+        os.makedirs(os.path.dirname(model_path), exist_ok=True)
+        joblib.dump(model, model_path)
+        training_time = time.time() - start_time
+        results = {
+            "model_type": "isolation_forest",
+            "model_path": model_path,
+            "auc_score": auc_score,
+            "training_time_seconds": training_time,
+        }
+        self.logger.info(f"Isolation Forest training completed in {training_time:.2f}s, AUC: {auc_score:.4f}")
+        return results
+
+    def save_training_metadata(self, results: Dict[str, Any]) -> None:
+        metadata = {
+            "timestamp": datetime.now().isoformat(),
+            "training_results": results,
+            "configuration": {
+                "test_size": self.test_size,
+                "validation_size": self.validation_size,
+                "random_state": self.random_state,
+            },
+        }
+        metadata_path = os.path.join(self.output_dir, "training_metadata.json")
+        with open(metadata_path, "w") as f:
+            json.dump(metadata, f, indent=2, default=float)
+        self.logger.info(f"Training metadata saved to: {metadata_path}")
