@@ -429,6 +429,78 @@ int fd_gbdt_fit_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n
 int fd_gbdt_fit_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F,
                          const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes, float* margins);
 
+/* ---------------------------------------------------------------- training: IsolationForest (ModelTrainer) */
+/* Replaces ModelTrainer.train_isolation_forest's fit (ml/training/model_trainer.py:235-276): grows the trees of a
+   scikit-learn IsolationForest (ExtraTreeRegressor(splitter="random", max_features=1) on max_samples rows drawn
+   without replacement) and places offset_ at the contamination percentile of the fit rows' scores. The result is an
+   fd_tree_arrays forest of kind FD_FOREST_SKLEARN_IFOREST that fd_load_forest serves. The arithmetic is the engine's
+   own and declared (csrc/iforest_fit_row.h); it follows scikit-learn's algorithm wherever that is
+   deterministic and replaces its Mersenne Twister stream by counter-based hashes, so the trees are not scikit-learn's
+   bit for bit. The device path (_device / _host) and the single-threaded reference (_ref_host) compile the same rule
+   header and return the same bits.
+
+   psi = max_samples == 0 ? min(256, n) : min(max_samples, n); D = ceil(log2(max(psi, 2))) (at most 10).
+   key = fmix64(seed + 0x9e3779b97f4a7c15); hash(t, a, tag) = fmix64(key ^ (t << 32 | a << 2 | tag)).
+   Sample: tree t's j-th row (j < psi) is perm_t(j): x = j, then x = feistel_t(x) until x < n, where feistel_t is a
+   4-round Feistel network on 2 b bits (b = ceil(ceil(log2 n) / 2), at least 1): (L, R) = (x >> b, x & (2^b - 1)),
+   per round r (L, R) = (R, L ^ (fmix64(hash(t, r, 3) ^ R) & (2^b - 1))), result L << b | R. A bijection of [0, n):
+   a tree's rows are distinct. max_features < 1 keeps the max(1, floor(max_features F)) features with the smallest
+   hash(t, f, 2), ties to the lower index.
+   Split: a node with m samples at depth d (heap index i, the root 0, children 2 i + 1 and 2 i + 2) is a leaf iff
+   m <= 1 or d == D or no kept feature has max > min over its samples (-0 == +0; a NaN enters neither). Otherwise, of
+   the c non-constant kept features in index order the r-th is split, r = (hash(t, i, 0) * c) >> 64; with mn, mx its
+   min and max widened to f64 and u = (hash(t, i, 1) >> 11) * 2^-53, thr = mn + u * (mx - mn) (two roundings, no
+   fma), and thr = mn unless thr < mx. A row goes left iff (double)x <= thr; default_left = 0 (a NaN goes right).
+   Leaf: leaf_value = ((d + 1) + c(m)) - 1, the term the scikit-learn loader builds; c(0) = c(1) = 0, c(2) = 1,
+   c(m) = 2 (ln(m - 1) + 0.5772156649015329) - 2 (m - 1) / m, one host table per fit. Nodes are numbered breadth-first
+   (a split node's children take the next two numbers); n_node_samples is the node's sample count.
+   if_denominator = n_estimators * c(psi). if_offset: -0.5 when contamination == 0; else the rows of X are scored with
+   the grown forest (raw = the f64 sum of the leaf values in tree order, what fd_forest_predict_* reports), the sums
+   sorted, and with pos = contamination (n - 1), k = floor(pos), g = pos - k, a = -2^(-raw[k] / denominator),
+   b = -2^(-raw[min(k + 1, n - 1)] / denominator): offset = g < 0.5 ? a + (b - a) g : b - (b - a) (1 - g), numpy's
+   linear percentile of score_samples. */
+typedef struct {
+  int32_t n_estimators; /* 1 .. 65536 */
+  int32_t max_samples;  /* 0: min(256, n); else 2 .. 1024, clamped to n */
+  double max_features;  /* (0, 1] */
+  double contamination; /* 0: "auto" (offset -0.5); else (0, 0.5] */
+  uint64_t seed;
+} fd_iforest_fit_params;
+
+/* The fit: X n x ld f32 (F <= min(ld, 64) model columns), 2 <= n <= 2^31 - 1 (FD_ERR_UNSUPPORTED above). Two calls, as
+   fd_gbdt_fit_*: with out == NULL *n_nodes receives the node capacity n_estimators * (2^(D + 1) - 1) and nothing runs;
+   with out (arrays of that capacity, tree_offsets n_estimators + 1; written despite their const) and n_node_samples
+   (that capacity, may be NULL) the forest is grown, *n_nodes receives its size and *forest its kind, num_feature,
+   if_offset and if_denominator. _device: d_X is a device pointer, the outputs host arrays; one workgroup grows one
+   tree, all trees come back in one copy, the offset's scoring and radix sort run on the device and two f64 come back.
+   FD_ERR_INVALID_ARG: n < 2, F outside 1..64, ld < F, a parameter outside its range, a non-finite value in X (_host
+   and _ref_host check; _device trusts the caller and still terminates). Counters "iforest_fit_trees",
+   "iforest_fit_nodes_split". */
+int fd_iforest_fit_device(fd_engine* eng, const float* d_X, int64_t n, int32_t ld, int32_t F,
+                          const fd_iforest_fit_params* params, fd_tree_arrays* out, double* n_node_samples,
+                          fd_forest_params* forest, int64_t* n_nodes);
+int fd_iforest_fit_host(fd_engine* eng, const float* X, int64_t n, int32_t ld, int32_t F,
+                        const fd_iforest_fit_params* params, fd_tree_arrays* out, double* n_node_samples,
+                        fd_forest_params* forest, int64_t* n_nodes);
+int fd_iforest_fit_ref_host(const float* X, int64_t n, int32_t ld, int32_t F, const fd_iforest_fit_params* params,
+                            fd_tree_arrays* out, double* n_node_samples, fd_forest_params* forest, int64_t* n_nodes);
+/* Tree `tree`'s row ids perm_t(0 .. psi - 1) of a fit over n rows: rows holds 1024 entries, *psi receives the count.
+   _host computes them in a kernel, _ref_host in plain C++. Of params max_samples and seed are read. */
+int fd_iforest_fit_sample_host(fd_engine* eng, int64_t n, const fd_iforest_fit_params* params, int32_t tree,
+                               int32_t* rows, int32_t* psi);
+int fd_iforest_fit_sample_ref_host(int64_t n, const fd_iforest_fit_params* params, int32_t tree, int32_t* rows,
+                                   int32_t* psi);
+/* One tree from explicit row ids (m of them, 1 .. 1024, each in [0, n), need not be distinct; psi = m) and a feature
+   mask (bit f: feature f is kept), as tree `tree` of seed params->seed: the rows-in, tree-out seam of the split rule.
+   out's arrays hold 2^(D + 1) - 1 nodes and tree_offsets two entries; *n_nodes receives the tree's size. */
+int fd_iforest_fit_grow_tree_host(fd_engine* eng, const float* X, int64_t n, int32_t ld, int32_t F,
+                                  const int32_t* rows, int32_t m, uint64_t feature_mask,
+                                  const fd_iforest_fit_params* params, int32_t tree, fd_tree_arrays* out,
+                                  double* n_node_samples, int64_t* n_nodes);
+int fd_iforest_fit_grow_tree_ref_host(const float* X, int64_t n, int32_t ld, int32_t F, const int32_t* rows,
+                                      int32_t m, uint64_t feature_mask, const fd_iforest_fit_params* params,
+                                      int32_t tree, fd_tree_arrays* out, double* n_node_samples, int64_t* n_nodes);
+
 /* ---------------------------------------------------------------- blend (a11-a13) */
 /* Replaces _calculate_model_confidence + _combine_predictions + _make_decision +
    _calculate_risk_level (ml/models/ensemble_predictor.py:252-369) for a batch.
@@ -1297,6 +1369,8 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    "forest_shap_launches" (launches of the TreeSHAP kernel, fd_forest_shap_*),
    "gbdt_hist_launches" (launches of the GBDT fit's histogram kernel: one per tree level), "gbdt_trees" (trees grown
    on the device by fd_gbdt_fit_* / fd_gbdt_grow_tree_*), "gbdt_nodes_split" (split nodes of those trees),
+   "iforest_fit_trees" (IsolationForest trees grown on the device by fd_iforest_fit_device / _host /
+   _grow_tree_host), "iforest_fit_nodes_split" (split nodes of those trees),
    "mlp_launches" (launches of the MLP head's kernel), "graph_steps" (fd_graph_step_* calls with n > 0),
    "text_calls" (fd_text_features_device / _host calls with n > 0), "text_nonascii_rows" (rows those calls flagged
    FD_TEXT_NONASCII; reading it waits for the engine stream),

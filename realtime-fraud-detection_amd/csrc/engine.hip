@@ -439,6 +439,7 @@ int fd_engine_destroy(fd_engine* eng) {
   }
   e.shap_partial.release();
   fd::gbdt_release(e);
+  fd::iforest_fit_release(e);
   e.stage.release();
   e.scratch_probs.release();
   e.feat_vec.release();
@@ -607,6 +608,10 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
     *value = (int64_t)e.gbdt.trees;
   } else if (k == "gbdt_nodes_split") {  // split nodes of those trees
     *value = (int64_t)e.gbdt.nodes_split;
+  } else if (k == "iforest_fit_trees") {  // IsolationForest trees grown on the device (fd_iforest_fit_*)
+    *value = (int64_t)e.iforest.trees;
+  } else if (k == "iforest_fit_nodes_split") {  // split nodes of those trees
+    *value = (int64_t)e.iforest.nodes_split;
   } else if (k == "mlp_launches") {  // launches of the MLP head's kernel (fd_mlp_predict_*, FD_SLOT_MLP models)
     *value = (int64_t)e.mlp_total;
   } else if (k == "graph_steps") {  // fd_graph_step_* calls that appended transactions
@@ -1487,6 +1492,125 @@ int fd_gbdt_fit_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n
   st.upload();
   fd::gbdt_fit_staged(e, dX, n ? X : &none, dy, n, ld, F, *params, *out, n_nodes, dm);
   st.download();
+  FD_API_END
+}
+
+// ---------------------------------------------------------------- training: IsolationForest (iforest_fit.hip)
+
+// the first of the two calls: only the node capacity
+static void iforest_fit_capacity(const fd_iforest_fit_params& p, int64_t n, int32_t ld, int32_t F, int64_t* n_nodes) {
+  fd::iforest_fit_check(p, n, ld, F);
+  FD_REQUIRE(n_nodes, FD_ERR_INVALID_ARG, "iforest_fit: null n_nodes");
+  *n_nodes = fd::iforest_fit_capacity(p, n);
+}
+
+int fd_iforest_fit_ref_host(const float* X, int64_t n, int32_t ld, int32_t F, const fd_iforest_fit_params* params,
+                            fd_tree_arrays* out, double* n_node_samples, fd_forest_params* forest, int64_t* n_nodes) {
+  FD_API_BEGIN
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "iforest_fit: null params");
+  if (!out) {
+    iforest_fit_capacity(*params, n, ld, F, n_nodes);
+    return FD_OK;
+  }
+  FD_REQUIRE(X && forest, FD_ERR_INVALID_ARG, "iforest_fit: null X / forest");
+  fd::iforest_fit_ref_host(X, n, ld, F, *params, *out, n_node_samples, *forest, n_nodes);
+  FD_API_END
+}
+
+int fd_iforest_fit_device(fd_engine* eng, const float* d_X, int64_t n, int32_t ld, int32_t F,
+                          const fd_iforest_fit_params* params, fd_tree_arrays* out, double* n_node_samples,
+                          fd_forest_params* forest, int64_t* n_nodes) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "iforest_fit: null params");
+  if (!out) {
+    iforest_fit_capacity(*params, n, ld, F, n_nodes);
+    return FD_OK;
+  }
+  FD_REQUIRE(d_X && forest, FD_ERR_INVALID_ARG, "iforest_fit: null X / forest");
+  fd::iforest_fit_device(e, d_X, n, ld, F, *params, *out, n_node_samples, *forest, n_nodes);
+  FD_API_END
+}
+
+int fd_iforest_fit_host(fd_engine* eng, const float* X, int64_t n, int32_t ld, int32_t F,
+                        const fd_iforest_fit_params* params, fd_tree_arrays* out, double* n_node_samples,
+                        fd_forest_params* forest, int64_t* n_nodes) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "iforest_fit: null params");
+  if (!out) {
+    iforest_fit_capacity(*params, n, ld, F, n_nodes);
+    return FD_OK;
+  }
+  fd::iforest_fit_check(*params, n, ld, F);
+  FD_REQUIRE(X && forest, FD_ERR_INVALID_ARG, "iforest_fit: null X / forest");
+  fd::iforest_fit_check_finite(X, n, ld, F);
+  Stage st(e);
+  const float* dX;
+  st.in(dX, X, (size_t)n * ld);
+  st.upload();
+  fd::iforest_fit_device(e, dX, n, ld, F, *params, *out, n_node_samples, *forest, n_nodes);
+  FD_API_END
+}
+
+// what the two sample seams check before a row id is computed
+static void iforest_sample_check(int64_t n, const fd_iforest_fit_params* params, int32_t tree, const int32_t* rows) {
+  FD_REQUIRE(params && rows, FD_ERR_INVALID_ARG, "iforest_fit: null params / rows");
+  fd::iforest_fit_check(*params, n, 1, 1);
+  FD_REQUIRE(tree >= 0 && tree < 65536, FD_ERR_INVALID_ARG, "iforest_fit: tree must be in 0..65535");
+}
+
+int fd_iforest_fit_sample_ref_host(int64_t n, const fd_iforest_fit_params* params, int32_t tree, int32_t* rows,
+                                   int32_t* psi) {
+  FD_API_BEGIN
+  iforest_sample_check(n, params, tree, rows);
+  fd::iforest_fit_sample_ref_host(n, *params, tree, rows, psi);
+  FD_API_END
+}
+
+int fd_iforest_fit_sample_host(fd_engine* eng, int64_t n, const fd_iforest_fit_params* params, int32_t tree,
+                               int32_t* rows, int32_t* psi) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  iforest_sample_check(n, params, tree, rows);
+  fd::iforest_fit_sample_device(e, n, *params, tree, rows, psi);
+  FD_API_END
+}
+
+static void iforest_grow_check(const float* X, int64_t n, int32_t ld, int32_t F, const fd_iforest_fit_params* params,
+                               int32_t tree, const fd_tree_arrays* out) {
+  FD_REQUIRE(params && out && X, FD_ERR_INVALID_ARG, "iforest_fit: null params / out / X");
+  FD_REQUIRE(n >= 1 && n <= 2147483647ll && F >= 1 && F <= 64 && ld >= F, FD_ERR_INVALID_ARG,
+             "iforest_fit: n must be in 1..2^31 - 1, F in 1..64 and ld >= F");
+  FD_REQUIRE(tree >= 0 && tree < 65536, FD_ERR_INVALID_ARG, "iforest_fit: tree must be in 0..65535");
+}
+
+int fd_iforest_fit_grow_tree_ref_host(const float* X, int64_t n, int32_t ld, int32_t F, const int32_t* rows,
+                                      int32_t m, uint64_t feature_mask, const fd_iforest_fit_params* params,
+                                      int32_t tree, fd_tree_arrays* out, double* n_node_samples, int64_t* n_nodes) {
+  FD_API_BEGIN
+  iforest_grow_check(X, n, ld, F, params, tree, out);
+  fd::iforest_fit_grow_tree_ref_host(X, n, ld, F, rows, m, feature_mask, *params, tree, *out, n_node_samples, n_nodes);
+  FD_API_END
+}
+
+int fd_iforest_fit_grow_tree_host(fd_engine* eng, const float* X, int64_t n, int32_t ld, int32_t F,
+                                  const int32_t* rows, int32_t m, uint64_t feature_mask,
+                                  const fd_iforest_fit_params* params, int32_t tree, fd_tree_arrays* out,
+                                  double* n_node_samples, int64_t* n_nodes) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  iforest_grow_check(X, n, ld, F, params, tree, out);
+  Stage st(e);
+  const float* dX;
+  st.in(dX, X, (size_t)n * ld);
+  st.upload();
+  fd::iforest_fit_grow_tree_device(e, dX, n, ld, F, rows, m, feature_mask, *params, tree, *out, n_node_samples,
+                                   n_nodes);
   FD_API_END
 }
 

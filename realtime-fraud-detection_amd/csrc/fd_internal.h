@@ -235,6 +235,14 @@ struct PackedForest {
   mutable ShapImage shap;
 };
 
+// iforest_fit.hip: device buffers of a fit (they grow and stay), the grown forest packed for the offset's scoring pass
+// (never in a slot) and the counters "iforest_fit_trees" / "iforest_fit_nodes_split"
+struct IForestFitScratch {
+  DeviceBuffer rows, masks, heaps, raw, prob, sorted, sort_tmp;
+  PackedForest scorer;
+  unsigned long long trees = 0, nodes_split = 0;
+};
+
 // The fused ensemble kernel's joint repack of one XGBoost and/or one IsolationForest (ensemble_plan.hip build_plan):
 // both padded to one depth D, node words rewritten against the MERGED per-feature threshold tables, so one bin
 // tile serves both forests; chunks of CH[k] node-only trees, leaf values [tree][2^D] per forest.
@@ -739,6 +747,7 @@ struct Engine {
   unsigned long long shap_total = 0;          // counter "forest_shap_launches": launches of shap_kernel
   DeviceBuffer shap_partial;                  // shap.hip: per-chunk sums of one row batch, [chunk][column][row]
   GbdtScratch gbdt;                           // gbdt.hip: the fit's device buffers and counters
+  IForestFitScratch iforest;                  // iforest_fit.hip: the fit's device buffers and counters
   unsigned long long ens_single_total = 0;    // counter "ensemble_single_launches": fd_forest_predict batches run by
                                               // the fused kernel over one forest (config 2's timed kernel)
   unsigned long long pipe_split_total = 0;    // counter "pipelined_split_batches": of those, split rows
@@ -1056,6 +1065,28 @@ void gbdt_fit_device(Engine& e, const float* d_X, const uint8_t* d_y, int64_t n,
 void gbdt_fit_staged(Engine& e, const float* d_X, const float* h_X, const uint8_t* d_y, int64_t n, int32_t ld,
                      int32_t F, const fd_gbdt_params& p, const fd_gbdt_model& out, int64_t* n_nodes, float* d_margins);
 void gbdt_release(Engine& e);
+
+// iforest_fit.hip: the IsolationForest fit (include/fdengine.h "training: IsolationForest"; the rule is
+// iforest_fit_row.h). Host pointers unless named d_*; the outputs are host arrays.
+void iforest_fit_check(const fd_iforest_fit_params& p, int64_t n, int32_t ld, int32_t F);
+int iforest_fit_psi(const fd_iforest_fit_params& p, int64_t n);
+int64_t iforest_fit_capacity(const fd_iforest_fit_params& p, int64_t n);
+void iforest_fit_check_finite(const float* X, int64_t n, int32_t ld, int32_t F);
+void iforest_fit_ref_host(const float* X, int64_t n, int32_t ld, int32_t F, const fd_iforest_fit_params& p,
+                          fd_tree_arrays& out, double* n_node_samples, fd_forest_params& forest, int64_t* n_nodes);
+void iforest_fit_device(Engine& e, const float* d_X, int64_t n, int32_t ld, int32_t F, const fd_iforest_fit_params& p,
+                        fd_tree_arrays& out, double* n_node_samples, fd_forest_params& forest, int64_t* n_nodes);
+void iforest_fit_sample_ref_host(int64_t n, const fd_iforest_fit_params& p, int32_t tree, int32_t* rows, int32_t* psi);
+void iforest_fit_sample_device(Engine& e, int64_t n, const fd_iforest_fit_params& p, int32_t tree, int32_t* rows,
+                               int32_t* psi);
+void iforest_fit_grow_tree_ref_host(const float* X, int64_t n, int32_t ld, int32_t F, const int32_t* rows, int32_t m,
+                                    uint64_t feature_mask, const fd_iforest_fit_params& p, int32_t tree,
+                                    fd_tree_arrays& out, double* n_node_samples, int64_t* n_nodes);
+// d_X: the matrix on the device; rows: host ids (checked by the caller)
+void iforest_fit_grow_tree_device(Engine& e, const float* d_X, int64_t n, int32_t ld, int32_t F, const int32_t* rows,
+                                  int32_t m, uint64_t feature_mask, const fd_iforest_fit_params& p, int32_t tree,
+                                  fd_tree_arrays& out, double* n_node_samples, int64_t* n_nodes);
+void iforest_fit_release(Engine& e);
 // shap.hip: path-dependent TreeSHAP (include/fdengine.h "forest attribution")
 struct ShapTable {
   std::vector<fd_shap_path> paths;

@@ -143,6 +143,11 @@ class fd_gbdt_model(C.Structure):
                 ("base_weights", C.c_void_p)]
 
 
+class fd_iforest_fit_params(C.Structure):
+    _fields_ = [("n_estimators", C.c_int32), ("max_samples", C.c_int32), ("max_features", C.c_double),
+                ("contamination", C.c_double), ("seed", C.c_uint64)]
+
+
 class fd_state_params(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("window_mode", C.c_int32), ("ring_k", C.c_int32), ("seq_len", C.c_int32)]
 
@@ -544,6 +549,22 @@ SIGNATURES = {
                                    C.POINTER(fd_gbdt_model), C.POINTER(_i64), _vp]),
     "fd_gbdt_fit_ref_host": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.POINTER(fd_gbdt_params),
                                        C.POINTER(fd_gbdt_model), C.POINTER(_i64), _vp]),
+    "fd_iforest_fit_device": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.POINTER(fd_iforest_fit_params),
+                                        C.POINTER(fd_tree_arrays), _vp, C.POINTER(fd_forest_params), C.POINTER(_i64)]),
+    "fd_iforest_fit_host": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.POINTER(fd_iforest_fit_params),
+                                      C.POINTER(fd_tree_arrays), _vp, C.POINTER(fd_forest_params), C.POINTER(_i64)]),
+    "fd_iforest_fit_ref_host": (C.c_int, [_vp, _i64, _i32, _i32, C.POINTER(fd_iforest_fit_params),
+                                          C.POINTER(fd_tree_arrays), _vp, C.POINTER(fd_forest_params),
+                                          C.POINTER(_i64)]),
+    "fd_iforest_fit_sample_host": (C.c_int, [_vp, _i64, C.POINTER(fd_iforest_fit_params), _i32, _vp,
+                                             C.POINTER(_i32)]),
+    "fd_iforest_fit_sample_ref_host": (C.c_int, [_i64, C.POINTER(fd_iforest_fit_params), _i32, _vp, C.POINTER(_i32)]),
+    "fd_iforest_fit_grow_tree_host": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, C.c_uint64,
+                                                C.POINTER(fd_iforest_fit_params), _i32, C.POINTER(fd_tree_arrays),
+                                                _vp, C.POINTER(_i64)]),
+    "fd_iforest_fit_grow_tree_ref_host": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, C.c_uint64,
+                                                    C.POINTER(fd_iforest_fit_params), _i32,
+                                                    C.POINTER(fd_tree_arrays), _vp, C.POINTER(_i64)]),
 }
 
 

@@ -253,8 +253,37 @@ class FraudEngine:
         return _gbdt_grow("fd_gbdt_grow_tree_host", (self._h,), bins, cuts, offsets, g, h, row_mask, feature_mask,
                           params)
 
+    # ------------------------------------------------------------------ training (IsolationForest, iforest_fit.hip)
+    def fit_iforest(self, X, **params) -> ForestArrays:
+        """Grow an IsolationForest on the engine and place its offset (fd_iforest_fit_*; the declared semantics are
+        DESIGN §4.15). X: [n >= 2, F <= 64] numpy (finite values), or a contiguous f32 torch tensor on this engine's
+        device. params: IFOREST_DEFAULTS (n_estimators, max_samples, max_features, contamination, seed; random_state
+        is accepted for seed, "auto" for contamination 0 and for max_samples 0). -> ForestArrays ready for
+        load_forest, cover = the nodes' sample counts, if_offset, if_denominator, meta["max_samples"] (psi),
+        meta["n_node_samples"] and the parameters under their names. num_feature=F: only the first F columns of X are
+        the model's (the rows are wider)."""
+        F = params.pop("num_feature", None)
+        p = iforest_fit_params(**params)
+        if type(X).__module__.startswith("torch") and X.is_cuda:
+            import torch
+            if X.dtype != torch.float32 or X.dim() != 2 or not X.is_contiguous():
+                raise ValueError("device input: a contiguous 2-d float32 tensor")
+            n, ld = X.shape
+            torch.cuda.current_stream(X.device).synchronize()
+            return _iforest_fit("fd_iforest_fit_device", (self._h,), C.c_void_p(X.data_ptr()), n, ld, F, p)
+        X = _iforest_x(X)
+        return _iforest_fit("fd_iforest_fit_host", (self._h,), _ptr(X), X.shape[0], X.shape[1], F, p)
+
+    def iforest_fit_sample(self, n: int, tree: int, **params) -> np.ndarray:
+        """Tree `tree`'s row ids of a fit over n rows, by the sample kernel (fd_iforest_fit_sample_host)."""
+        return _iforest_sample("fd_iforest_fit_sample_host", (self._h,), n, tree, params)
+
+    def iforest_fit_grow_tree(self, X, rows, tree: int = 0, feature_mask=None, **params) -> ForestArrays:
+        """One tree from explicit row ids, by the grow kernel (fd_iforest_fit_grow_tree_host)."""
+        return _iforest_grow("fd_iforest_fit_grow_tree_host", (self._h,), X, rows, tree, feature_mask, params)
+
     # ------------------------------------------------------------------ card state + features
-    _TXN_DTYPES = {"card_key": np.uint64, "ts_ms": np.int64, "amount_cents": np.int64, "merchant": np.int32,
+    _TXN_DTYPES ={"card_key": np.uint64, "ts_ms": np.int64, "amount_cents": np.int64, "merchant": np.int32,
                    "device_fp": np.uint64, "ip_class": np.uint8, "hour": np.uint8, "weekend": np.uint8}
 
     def state_init(self, capacity: int, window_mode: int = N.FD_WINDOW_REDIS_COMPAT, ring_k: int = 16,
@@ -1255,6 +1284,117 @@ def gbdt_grow_tree_ref_host(bins, cuts, offsets, g, h, row_mask=None, feature_ma
     """Host-only: one tree from a binned matrix and fixed-point gradients (fd_gbdt_grow_tree_ref_host). feature_mask:
     an integer whose bit f keeps feature f (None: all)."""
     return _gbdt_grow("fd_gbdt_grow_tree_ref_host", (), bins, cuts, offsets, g, h, row_mask, feature_mask, params)
+
+
+# ------------------------------------------------------------------------------------ training (iforest_fit.hip)
+
+IFOREST_DEFAULTS = dict(n_estimators=100, max_samples=0, max_features=1.0, contamination=0.0, seed=0)
+
+
+def iforest_fit_params(**kw) -> "N.fd_iforest_fit_params":
+    """fd_iforest_fit_params from keywords (IFOREST_DEFAULTS; scikit-learn's random_state is accepted for seed and
+    "auto" for max_samples and contamination)."""
+    v = dict(IFOREST_DEFAULTS)
+    for k, x in kw.items():
+        k = {"random_state": "seed"}.get(k, k)
+        if k not in v:
+            raise TypeError(f"unknown IsolationForest parameter {k!r}")
+        v[k] = 0 if isinstance(x, str) and x == "auto" and k in ("max_samples", "contamination") else x
+    return N.fd_iforest_fit_params(int(v["n_estimators"]), int(v["max_samples"]), float(v["max_features"]),
+                                   float(v["contamination"]), int(v["seed"]) & (2 ** 64 - 1))
+
+
+def _iforest_x(X) -> np.ndarray:
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float32))
+    if X.ndim != 2:
+        raise ValueError("X: a 2-d matrix")
+    return X
+
+
+class _IForestOut:
+    """Caller arrays of a grown IsolationForest with room for `cap` nodes of `n_trees` trees."""
+
+    def __init__(self, n_trees: int, cap: int):
+        self.a = dict(offsets=np.zeros(n_trees + 1, np.int64), left=np.zeros(cap, np.int32),
+                      right=np.zeros(cap, np.int32), feature=np.zeros(cap, np.int32),
+                      threshold=np.zeros(cap, np.float64), default_left=np.zeros(cap, np.uint8),
+                      leaf_value=np.zeros(cap, np.float64), n_node_samples=np.zeros(cap, np.float64))
+        a = self.a
+
+        def P(x, t):
+            return x.ctypes.data_as(C.POINTER(t))
+
+        self.trees = N.fd_tree_arrays(n_trees, P(a["offsets"], C.c_int64), P(a["left"], C.c_int32),
+                                      P(a["right"], C.c_int32), P(a["feature"], C.c_int32),
+                                      P(a["threshold"], C.c_double), P(a["default_left"], C.c_uint8),
+                                      P(a["leaf_value"], C.c_double))
+
+    def forest(self, n_nodes: int, num_feature: int, fp=None, **meta) -> ForestArrays:
+        a = {k: (v if k == "offsets" else v[:n_nodes].copy()) for k, v in self.a.items()}
+        return ForestArrays(kind=N.FD_FOREST_SKLEARN_IFOREST, num_feature=num_feature, offsets=a["offsets"],
+                            left=a["left"], right=a["right"], feature=a["feature"], threshold=a["threshold"],
+                            default_left=a["default_left"], leaf_value=a["leaf_value"],
+                            if_offset=fp.if_offset if fp is not None else 0.0,
+                            if_denominator=fp.if_denominator if fp is not None else 0.0, cover=a["n_node_samples"],
+                            meta=dict(meta, n_trees=len(a["offsets"]) - 1, n_node_samples=a["n_node_samples"]))
+
+
+def _iforest_fit(fn: str, head, xptr, n: int, ld: int, F, p) -> ForestArrays:
+    """The two calls of fd_iforest_fit_*: the capacity, then the fit. F: the model's columns (None: all ld)."""
+    F = int(ld if F is None else F)
+    cap = C.c_int64()
+    N.call(fn, *head, xptr, n, ld, F, C.byref(p), None, None, None, C.byref(cap))
+    out = _IForestOut(p.n_estimators, cap.value)
+    fp = N.fd_forest_params()
+    nn = C.c_int64()
+    N.call(fn, *head, xptr, n, ld, F, C.byref(p), C.byref(out.trees), out.a["n_node_samples"].ctypes.data,
+           C.byref(fp), C.byref(nn))
+    psi = min(p.max_samples or 256, n)
+    return out.forest(nn.value, F, fp, max_samples=psi, n_estimators=p.n_estimators, max_features=p.max_features,
+                      contamination=p.contamination, seed=p.seed)
+
+
+def iforest_fit_ref_host(X, **params) -> ForestArrays:
+    """Host-only: the single-threaded reference fit (fd_iforest_fit_ref_host), as FraudEngine.fit_iforest returns
+    it. num_feature=F: only the first F columns of X are the model's."""
+    X = _iforest_x(X)
+    F = params.pop("num_feature", None)
+    return _iforest_fit("fd_iforest_fit_ref_host", (), _ptr(X), X.shape[0], X.shape[1], F,
+                        iforest_fit_params(**params))
+
+
+def _iforest_sample(fn: str, head, n: int, tree: int, params) -> np.ndarray:
+    p = iforest_fit_params(**params)
+    rows = np.zeros(1024, np.int32)
+    psi = C.c_int32()
+    N.call(fn, *head, int(n), C.byref(p), int(tree), _ptr(rows), C.byref(psi))
+    return rows[:psi.value].copy()
+
+
+def iforest_fit_sample_ref_host(n: int, tree: int, **params) -> np.ndarray:
+    """Host-only: tree `tree`'s row ids of a fit over n rows (fd_iforest_fit_sample_ref_host)."""
+    return _iforest_sample("fd_iforest_fit_sample_ref_host", (), n, tree, params)
+
+
+def _iforest_grow(fn: str, head, X, rows, tree, feature_mask, params) -> ForestArrays:
+    X = _iforest_x(X)
+    n, F = X.shape
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    m = rows.size
+    fm = (2 ** F - 1) if feature_mask is None else int(feature_mask)
+    p = iforest_fit_params(**params)
+    depth = max(1, int(m - 1).bit_length())
+    out = _IForestOut(1, 2 ** (depth + 1) - 1)
+    nn = C.c_int64()
+    N.call(fn, *head, _ptr(X), n, F, F, _ptr(rows), m, C.c_uint64(fm), C.byref(p), int(tree), C.byref(out.trees),
+           out.a["n_node_samples"].ctypes.data, C.byref(nn))
+    return out.forest(nn.value, F, max_samples=m)
+
+
+def iforest_fit_grow_tree_ref_host(X, rows, tree: int = 0, feature_mask=None, **params) -> ForestArrays:
+    """Host-only: one tree from explicit row ids (fd_iforest_fit_grow_tree_ref_host). feature_mask: an integer whose
+    bit f keeps feature f (None: all)."""
+    return _iforest_grow("fd_iforest_fit_grow_tree_ref_host", (), X, rows, tree, feature_mask, params)
 
 
 def shard_of(keys, n_shards: int) -> np.ndarray:

@@ -242,6 +242,67 @@ def iforest_from_sklearn(model) -> ForestArrays:
                    if_denominator=denom, meta={"n_trees": len(trees)})
 
 
+def sklearn_iforest_from_forest(fa: ForestArrays, max_samples: Optional[int] = None, contamination=None):
+    """The inverse of iforest_from_sklearn: a scikit-learn IsolationForest holding the trees of `fa` (what
+    FraudEngine.fit_iforest returns), which joblib pickles and ModelManager loads like one scikit-learn fitted. The
+    training data is not needed: a template is fitted on two rows for its fitted attributes, then every estimator's
+    tree_ is rebuilt from fa's arrays through Tree.__setstate__ and the per-tree path-length arrays recomputed from
+    the rebuilt trees as IsolationForest.fit does. max_samples defaults to fa.meta["max_samples"], contamination to
+    fa.meta["contamination"] (0: "auto"); per-node sample counts come from fa.meta["n_node_samples"], then fa.cover.
+    Features are stored as the model's own columns (estimators_features_ is every column, whatever max_features
+    grew the trees)."""
+    from sklearn.ensemble import IsolationForest
+    from sklearn.ensemble._iforest import _average_path_length
+    from sklearn.tree._tree import Tree
+
+    if fa.kind != N.FD_FOREST_SKLEARN_IFOREST:
+        raise UnsupportedModel("only an IsolationForest has a scikit-learn IsolationForest form")
+    T, F = fa.n_trees, int(fa.num_feature)
+    psi = int(fa.meta["max_samples"] if max_samples is None else max_samples)
+    cont = fa.meta.get("contamination", 0.0) if contamination is None else contamination
+    cont = "auto" if isinstance(cont, str) or float(cont) == 0.0 else float(cont)
+    counts = fa.meta.get("n_node_samples", fa.cover)
+    if counts is None:
+        raise ValueError("the forest carries no per-node sample counts (meta['n_node_samples'] or cover)")
+    counts = np.asarray(counts, dtype=np.float64)
+    model = IsolationForest(n_estimators=T, max_samples=2, contamination="auto", random_state=0)
+    model.fit(np.arange(2 * F, dtype=np.float64).reshape(2, F))
+    node_dtype = model.estimators_[0].tree_.__getstate__()["nodes"].dtype
+    model._decision_path_lengths, model._average_path_length_per_tree = [], []
+    for tid, est in enumerate(model.estimators_):
+        s = slice(int(fa.offsets[tid]), int(fa.offsets[tid + 1]))
+        left = np.asarray(fa.left[s], np.int64)
+        leaf = left == -1
+        m = len(left)
+        nodes = np.zeros(m, dtype=node_dtype)
+        nodes["left_child"] = np.where(leaf, -1, left)
+        nodes["right_child"] = np.where(leaf, -1, np.asarray(fa.right[s], np.int64))
+        nodes["feature"] = np.where(leaf, -2, np.asarray(fa.feature[s], np.int64))
+        nodes["threshold"] = np.where(leaf, -2.0, np.asarray(fa.threshold[s], np.float64))
+        nodes["n_node_samples"] = counts[s].astype(np.int64)
+        nodes["weighted_n_node_samples"] = counts[s]
+        if "missing_go_to_left" in node_dtype.names:
+            nodes["missing_go_to_left"] = np.where(leaf, 0, np.asarray(fa.default_left[s], np.uint8))
+        depth = np.zeros(m, np.int64)
+        for i in np.nonzero(~leaf)[0]:  # breadth-first or any parent-before-child numbering
+            depth[left[i]] = depth[fa.right[s][i]] = depth[i] + 1
+        tree = Tree(F, np.array([1], dtype=np.intp), 1)
+        tree.__setstate__({"max_depth": int(depth.max()), "node_count": m, "nodes": nodes,
+                           "values": np.zeros((m, 1, 1), np.float64)})
+        est.tree_ = tree
+        est.max_features_ = 1
+        model._decision_path_lengths.append(tree.compute_node_depths())
+        model._average_path_length_per_tree.append(_average_path_length(tree.n_node_samples))
+    model.estimators_features_ = [np.arange(F) for _ in range(T)]
+    model.max_samples = psi
+    model.max_samples_ = psi
+    model._max_samples = psi
+    model._max_features = F
+    model.contamination = cont
+    model.offset_ = float(fa.if_offset)
+    return model
+
+
 def load_isolation_forest_joblib(path: str) -> ForestArrays:
     import joblib
     return iforest_from_sklearn(joblib.load(path))

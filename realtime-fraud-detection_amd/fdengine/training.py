@@ -1,5 +1,6 @@
 """Drop-in for the reference's ModelTrainer (ml/training/model_trainer.py): same constructor, attributes, method names,
-result keys and written paths; the XGBoost member is fitted, saved, reloaded and scored on the engine.
+result keys and written paths; both members, XGBoost and IsolationForest, are fitted, saved, reloaded and scored on
+the engine.
 
 What differs, on purpose:
 * train_xgboost_model fits with FraudEngine.fit_gbdt (csrc/gbdt.hip) at the reference's parameters (max_depth 6,
@@ -11,7 +12,13 @@ What differs, on purpose:
 * The stratified 80 / 20 split is this module's own (no sklearn.model_selection needed).
 * auc_score is the Mann-Whitney statistic over midranks of the engine's probabilities (equal to sklearn's
   roc_auc_score); feature_importance is the normalised mean gain per feature, XGBClassifier's default for gbtree.
-* train_isolation_forest delegates to scikit-learn (the engine serves the result; it does not fit it).
+* train_isolation_forest fits with FraudEngine.fit_iforest (csrc/iforest_fit.hip) at the reference's parameters (100
+  estimators, contamination 0.05, random_state as the seed, normal transactions only). The fit's arithmetic is the
+  engine's own declared one: the joblib file it writes is a scikit-learn IsolationForest that
+  scikit-learn and this engine load, but its trees are not the trees scikit-learn's random stream would have grown.
+  scikit-learn and joblib are needed for that file only; IsolationForest.fit never sees the training data.
+  auc_score is taken from the engine's raw path-length sums: -decision_function is decreasing in them, so the
+  midrank statistic is the reference's.
 """
 from __future__ import annotations
 
@@ -24,10 +31,11 @@ from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
 
-from .forest import ForestArrays, xgboost_doc_from_forest
+from .forest import ForestArrays, load_isolation_forest_joblib, sklearn_iforest_from_forest, xgboost_doc_from_forest
 
 ID_COLUMNS = ("is_fraud", "transaction_id", "user_id", "merchant_id")
 XGB_PARAMS = dict(max_depth=6, learning_rate=0.1, subsample=0.8, colsample_bytree=0.8, n_estimators=100)
+IFOREST_PARAMS = dict(n_estimators=100, contamination=0.05)
 
 
 def roc_auc_midrank(y_true, score) -> float:
@@ -75,7 +83,7 @@ def stratified_split(y, test_size: float, seed: int):
 
 
 class ModelTrainer:
-    """Trains the fraud models; the XGBoost member on the engine."""
+    """Trains the fraud models on the engine."""
 
     def __init__(self, output_dir: str = "/app/models", engine=None):
         self.logger = logging.getLogger("model_trainer")
@@ -218,17 +226,24 @@ class ModelTrainer:
 
     def train_isolation_forest(self, X_train: np.ndarray, y_train: np.ndarray, X_test: np.ndarray,
                                y_test: np.ndarray) -> Dict[str, Any]:
-        """scikit-learn fits the IsolationForest (ImportError without it); the engine serves the saved model."""
+        """The engine fits the IsolationForest; scikit-learn and joblib only carry the file (ImportError without)."""
         import joblib
-        from sklearn.ensemble import IsolationForest
         self.logger.info("Training Isolation Forest model...")
         start_time = time.time()
-        model = IsolationForest(contamination=0.05, n_estimators=100, random_state=self.random_state)
-        model.fit(X_train[y_train == 0])  # normal transactions only
-        auc_score = roc_auc_midrank(y_test, -model.decision_function(X_test))  # lower scores are more anomalous
+        eng = self.engine
+        X_normal = np.asarray(X_train)[np.asarray(y_train) == 0]  # normal transactions only
+        fa = eng.fit_iforest(X_normal, seed=self.random_state, **IFOREST_PARAMS)
         model_path = os.path.join(self.output_dir, "sklearn", "isolation_forest.joblib")
         os.makedirs(os.path.dirname(model_path), exist_ok=True)
-        joblib.dump(model, model_path)
+        joblib.dump(sklearn_iforest_from_forest(fa), model_path)
+        # score the held-out split with the file just written, as the serving side will
+        slot = self._free_slot(eng)
+        eng.load_forest(slot, load_isolation_forest_joblib(model_path))
+        try:
+            _, raw = eng.predict(slot, np.asarray(X_test, dtype=np.float32), want_raw=True)
+        finally:
+            eng.unload_forest(slot)
+        auc_score = roc_auc_midrank(y_test, -raw)  # shorter paths are more anomalous
         training_time = time.time() - start_time
         results = {
             "model_type": "isolation_forest",
