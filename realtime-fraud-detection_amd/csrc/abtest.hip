@@ -1,6 +1,7 @@
 // abtest.hip — the kernels of the A/B tests (ABTestManager, ml/testing/ab_testing.py): assign users to a variant,
 // partition a batch by variant for routed scoring, and reduce recorded results per variant. The per-row rule is
-// abtest_row.h; the routed scoring itself is fd_ab_score_matrix_* in engine.hip, which calls score_matrix twice.
+// abtest_row.h; the routed scoring itself is ab_score_matrix in score.hip (fd_ab_score_matrix_*), which calls
+// score_matrix once per variant.
 //
 // Partition (stable: control rows in arrival order, then treatment rows in arrival order; no atomic places a row).
 // A workgroup of kAbThreads takes kAbThreads consecutive rows, one per lane. Three launches:

@@ -25,25 +25,25 @@ __global__ void __launch_bounds__(256) blend_kernel(BlendConsts a, Cols cols, in
 
 }  // namespace
 
-void launch_blend(Engine& e, const fd_blend_params& p, int64_t n, const double* const* d_probs,
-                  const uint8_t* present, double* d_fp, double* d_conf, uint8_t* d_dec, uint8_t* d_risk) {
+void launch_blend(Engine& e, const ModelSet& ms, int64_t n, const double* const* d_probs, const ScoreOut& out) {
+  const fd_blend_params& p = *ms.params;
   FD_REQUIRE(p.n_models >= 0 && p.n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, "n_models out of range");
-  FD_REQUIRE(d_fp != nullptr, FD_ERR_INVALID_ARG, "null output");
+  FD_REQUIRE(out.fp != nullptr, FD_ERR_INVALID_ARG, "null output");
   if (n == 0) return;
-  const BlendConsts a = blend_consts(p, present);
+  const BlendConsts a = blend_consts(ms);
   FD_REQUIRE(a.n_models > 0, FD_ERR_INVALID_ARG, "No model predictions available");
   Cols cols{};
   int k = 0;
   for (int m = 0; m < p.n_models; ++m) {
-    if (present && !present[m]) continue;
+    if (!ms.has(m)) continue;
     FD_REQUIRE(d_probs && d_probs[m], FD_ERR_INVALID_ARG, "null probability column");
     cols.p[k++] = d_probs[m];
   }
   const int64_t blocks = (n + 255) / 256;
   Engine::Timed* ev = e.timing ? e.next_event_pair(FD_TIMING_BLEND) : nullptr;
   if (ev) FD_HIP(hipEventRecord(ev->a, e.stream));
-  hipLaunchKernelGGL(blend_kernel, dim3((unsigned)blocks), dim3(256), 0, e.stream, a, cols, n, d_fp, d_conf, d_dec,
-                     d_risk);
+  hipLaunchKernelGGL(blend_kernel, dim3((unsigned)blocks), dim3(256), 0, e.stream, a, cols, n, out.fp, out.conf,
+                     out.dec, out.risk);
   FD_HIP(hipGetLastError());
   if (ev) FD_HIP(hipEventRecord(ev->b, e.stream));
 }

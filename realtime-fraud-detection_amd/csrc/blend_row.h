@@ -100,11 +100,12 @@ struct Cols {
 };
 
 // the present models of fd_blend_params (failed / absent models dropped: weights renormalise over the rest)
-inline BlendConsts blend_consts(const fd_blend_params& p, const uint8_t* present) {
+inline BlendConsts blend_consts(const ModelSet& ms) {
+  const fd_blend_params& p = *ms.params;
   BlendConsts a{};
   int k = 0;
   for (int m = 0; m < p.n_models; ++m) {
-    if (present && !present[m]) continue;
+    if (!ms.has(m)) continue;
     a.weight[k] = p.weight[m];
     a.mult[k] = p.conf_mult[m];
     ++k;

@@ -1,4 +1,4 @@
-// Card-hash sharding over RCCL, driven by the engine itself (fd_comm_* / fd_sharded_step, engine.hip).
+// Card-hash sharding over RCCL, driven by the engine itself (fd_comm_* / fd_sharded_step: sharded_step below).
 //
 // The reference partitions per-card work by key across Kafka partitions and Flink's keyBy(userId)
 // (fl/FraudDetectionJob.java, WindowProcessor.java:44,63). Here each GPU owns the cards of its hash range and a
@@ -333,8 +333,7 @@ void exchange_ops(Engine& e, bool back, hipStream_t st, const void* sendbuf, con
 // slot s's records to their owners on the forward stream, into the next inbox of the ring (after the scoring
 // that last read it); with `next`, the next batch's count exchange in the same group (one RCCL launch for both:
 // per peer pair the records' send / receive precede the counts' on every rank), then its publish + places
-void comm_forward_group(Engine& e, int s, const fd_txn_batch* next, int64_t next_n, hipEvent_t next_ready, int ns,
-                        HostLaps& L) {
+void comm_forward_group(Engine& e, int s, const ShardBatch* next, int ns, HostLaps& L) {
   ShardComm& c = e.comm;
   const RcclApi& R = api(c);
   const int G = c.world;
@@ -342,7 +341,7 @@ void comm_forward_group(Engine& e, int s, const fd_txn_batch* next, int64_t next
   const int64_t* recv = c.split[s] + G;
   int64_t m = 0;
   for (int p = 0; p < G; ++p) m += recv[p];
-  if (next) counts_pre(e, *next, next_n, next_ready, ns);
+  if (next) counts_pre(e, *next->txns, next->n, next->ready, ns);
   L(1);
   const int q = c.inbox_next;
   c.inbox_next = (q + 1) % ShardComm::kInbox;
@@ -357,7 +356,7 @@ void comm_forward_group(Engine& e, int s, const fd_txn_batch* next, int64_t next
   FD_HIP(hipEventRecord(c.in_ev[q], c.x_fwd));
   if (next && c.count_gather) counts_gather(e, ns);
   L(4);
-  if (next) counts_post(e, *next, next_n, ns);
+  if (next) counts_post(e, *next->txns, next->n, ns);
   L(3);
 }
 
@@ -397,6 +396,77 @@ void comm_exchange(Engine& e, bool back, hipStream_t st, const void* sendbuf, co
   check(R, R.group_start(), "ncclGroupStart");
   exchange_ops(e, back, st, sendbuf, send, recvbuf, recv, elem);
   check(R, R.group_end(), "ncclGroupEnd");
+}
+
+// fd_sharded_step behind its argument checks: the step's operations in their one order (engine.hip holds the lock)
+void sharded_step(Engine& e, const ModelSet& ms, const ShardBatch& cur, const ShardBatch* next, const ScoreOut& out,
+                  int64_t* split_sizes) {
+  ShardComm& c = e.comm;
+  const int64_t n = cur.n;
+  // the prefetched batch is named by its id: batch_id 0 drops a pending prefetch (on every rank alike: its count
+  // exchange completes, its records are never sent); any other id must be the pending one
+  const bool use_pending = cur.id != 0;
+  if (use_pending)
+    FD_REQUIRE(c.pending && cur.id == c.pending_id && n == c.pending_n, FD_ERR_INVALID_ARG,
+               "batch " + std::to_string(cur.id) + " (n " + std::to_string(n) + ") is not the prefetched batch " +
+                   std::to_string(c.pending_id) + " (n " + std::to_string(c.pending_n) +
+                   "): pass its id, or 0 to drop the prefetch");
+  const int G = c.world;
+  HostLaps L{c};
+  c.steps.fetch_add(1, std::memory_order_relaxed);
+  // Every communicator operation below is issued by this thread in one fixed order on every rank:
+  //   [counts of this batch, when not prefetched] -> {records of this batch + counts of `next`: one group}
+  //   (x_fwd, fwd comm) -> results of this batch (engine stream, back comm)
+  // 1. this batch's split sizes: exchanged by the previous call (prefetch) or now
+  int s;
+  if (use_pending) {
+    s = c.pending_slot;
+  } else {
+    s = c.next_slot;
+    c.next_slot ^= 1;
+    comm_launch_counts(e, *cur.txns, n, cur.ready, s, L);
+  }
+  c.pending = false;
+  comm_wait_counts(e, s, n, L);  // the step's one host wait (a prefetched batch's counts landed a step ago)
+  const int64_t* send = c.split[s];
+  const int64_t* recv = c.split[s] + G;
+  if (split_sizes)
+    for (int p = 0; p < 2 * G; ++p) split_sizes[p] = c.split[s][p];
+  int64_t m = 0;
+  for (int p = 0; p < G; ++p) m += recv[p];
+  // 2. this batch's records to their owners and the next batch's counts, one group on the forward stream (after the
+  // owner's previous use of the inbox slot): the counts land while this batch is scored, and the next call's wait
+  // is satisfied
+  int ns = -1;
+  if (next) {
+    ns = c.next_slot;
+    c.next_slot ^= 1;
+    c.pending = true;
+    c.pending_id = next->id;
+    c.pending_n = next->n;
+    c.pending_slot = ns;
+  }
+  comm_forward_group(e, s, next, ns, L);
+  // 3. the owner's features + scoring on the pipeline (features wait for the records), results on the engine stream
+  const int q = c.inbox_of[s];
+  if (m) {
+    PipeBatch b;
+    b.records = c.inbox[q].ptr;
+    b.n = m;
+    b.d_results = c.res[q].ptr;
+    b.input_ready = c.in_ev[q];
+    b.results_in_place = true;
+    pipe_step(e, ms, b);
+  }
+  L(5);
+  // 4. results back (reversed splits) and into arrival order, on the engine stream
+  c.back_buf.ensure_headroom((size_t)std::max<int64_t>(n, 1) * sizeof(ResultRecord));
+  comm_exchange(e, true, e.stream, c.res[q].ptr, recv, c.back_buf.ptr, send, sizeof(ResultRecord));
+  FD_HIP(hipEventRecord(c.inbox_ev[q], e.stream));  // the engine stream has passed this batch's results: inbox q
+  c.inbox_live[q] = true;                           // and res[q] are free for batch i + 3
+  L(6);
+  if (n) launch_result_scatter(e, c.back_buf.ptr, n, out);
+  L(7);
 }
 
 }  // namespace fd

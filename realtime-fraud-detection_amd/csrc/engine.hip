@@ -1,4 +1,6 @@
-// engine.hip — C-ABI surface of libfdengine.so (declared in include/fdengine.h).
+// engine.hip — C-ABI surface of libfdengine.so (declared in include/fdengine.h), and nothing else: an entry point
+// locks the engine, checks its arguments, stages host arrays where it takes them, and makes one call into the
+// translation unit that does the work (the scoring schedulers: score.hip; the sharded step: comm.hip).
 // Every entry point catches everything: status codes + a thread-local message cross the ABI,
 // exceptions never do (mirrors the reference's log-and-raise contract, ml/models/model_manager.py:302-307,
 // with the raise done by the Python shim).
@@ -75,11 +77,11 @@ static std::recursive_mutex& lock_of(fd_engine* p) {
 #define FD_ENGINE_LOCK(p) std::lock_guard<std::recursive_mutex> fd_engine_guard_(lock_of(p))
 
 // Engine of an entry point that may queue work on e.stream: the next fd_score_batch_pipelined orders its
-// feature stream after e.stream again (pipe_dirty).
+// feature stream after e.stream again (Pipeline::dirty).
 static Engine& E(fd_engine* p) {
   FD_REQUIRE(p != nullptr, FD_ERR_INVALID_ARG, "null engine");
   p->e.activate();
-  p->e.pipe_dirty = true;
+  p->e.pipe.dirty = true;
   return p->e;
 }
 
@@ -90,292 +92,9 @@ static Engine& E_quiet(fd_engine* p) {
   return p->e;
 }
 
-// Events that only order one device's streams: no system-scope release at record (that is an L2 writeback
-// per record, several us of stream time between a kernel and its cross-stream dependents)
-constexpr unsigned kStreamEventFlags = hipEventDisableTiming | hipEventDisableSystemFence;
-
-static fd::PackedForest& slot_of(Engine& e, int slot) {
-  FD_REQUIRE(slot >= 0 && slot < fd::kMaxSlots, FD_ERR_INVALID_ARG, "slot out of range");
-  return e.forests[slot];
-}
-
-// Score the same feature matrix with every forest model, then blend (all on e.stream). A model in slot
-// FD_SLOT_LSTM runs the LSTM head over d_seq (n x T x 16) on the auxiliary stream, forked after
-// everything already queued on e.stream (the feature kernel that wrote d_seq) and joined before the blend. A model in
-// slot FD_SLOT_MLP is the MLP head over dX (mlp.hip), on e.stream beside the forests.
-// Returns true when the route result records were written too (the fused ensemble kernel writes them in its
-// epilogue); otherwise the caller packs them from the columns.
-static bool score_matrix(Engine& e, const fd_blend_params& p, const int32_t* slots, const double* const* ext,
-                         const uint8_t* present, const float* dX, int64_t n, int32_t ld, double* dMP,
-                         double* dfp, double* dconf, uint8_t* ddec, uint8_t* drisk, const float* d_seq = nullptr,
-                         int T = 0, const fd::RouteRecord* records = nullptr, fd::ResultRecord* results = nullptr,
-                         int compact = 0, const unsigned long long* d_seq_desc = nullptr) {
-  FD_REQUIRE(p.n_models > 0 && p.n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, "n_models out of range");
-  FD_REQUIRE(slots != nullptr && (dfp != nullptr || results != nullptr), FD_ERR_INVALID_ARG, "null slots/output");
-  if (n == 0) return false;
-  // one XGBoost + one IsolationForest, large batch: both forests and the blend in one kernel
-  if (fd::launch_ensemble(e, p, slots, present, dX, n, ld, dMP, dfp, dconf, ddec, drisk, records, results, compact))
-    return results != nullptr;
-  // compact vectors are written only when the fused kernel applies (pipe_step): any other path is a bug
-  FD_REQUIRE(!compact, FD_ERR_UNSUPPORTED, "internal: compact vectors without the fused ensemble kernel");
-  FD_REQUIRE(dfp != nullptr, FD_ERR_INVALID_ARG, "null output");
-  const int M = p.n_models;
-  if (!dMP) {
-    e.scratch_probs.ensure((size_t)n * M * sizeof(double));
-    dMP = e.scratch_probs.as<double>();
-  }
-  const double* cols[FD_MAX_MODELS] = {};
-  // small (latency) batches, small_streams: 0 (default) everything on e.stream — the kernels of a 1 k batch are
-  // short and the cross-queue fork / join hops cost more than the overlap gains (config 5: 0.088 vs 0.095 ms);
-  // 1 the LSTM and every forest after the first on aux; 2 the LSTM on aux, the other forests on aux2 (forked
-  // after everything queued so far, i.e. the feature kernel). Large batches: the LSTM on aux.
-  int n_forests = 0;
-  auto is_forest = [&](int m) { return slots[m] >= 0 && slots[m] != FD_SLOT_LSTM && slots[m] != FD_SLOT_MLP; };
-  for (int m = 0; m < M; ++m) n_forests += (!(present && !present[m]) && is_forest(m));
-  const bool latency = (n + fd::kTile - 1) / fd::kTile < fd::kSplitTiles;
-  const int ss = latency ? e.small_streams : 2;
-  const bool small = latency && n_forests > 1;
-  bool aux_forked = false;
-  auto fork_aux = [&]() {
-    if (aux_forked) return;
-    if (!e.aux_stream) {
-      FD_HIP(hipStreamCreateWithFlags(&e.aux_stream, hipStreamNonBlocking));
-      FD_HIP(hipEventCreateWithFlags(&e.fork_ev, kStreamEventFlags));
-      FD_HIP(hipEventCreateWithFlags(&e.join_ev, kStreamEventFlags));
-    }
-    FD_HIP(hipEventRecord(e.fork_ev, e.stream));
-    FD_HIP(hipStreamWaitEvent(e.aux_stream, e.fork_ev, 0));
-    aux_forked = true;
-  };
-  // option latency_prebin: when this call runs the pair path below on e.stream (two forests, every other present
-  // model the LSTM head), the LSTM launch bins the vectors for the pair's walks in workgroups ahead of its own, and
-  // the pair skips its binning launch (fd::PreBin; the bins are for this call only)
-  struct PreBinReset {
-    Engine& e;
-    ~PreBinReset() { e.prebin.want = e.prebin.done = false; }
-  } prebin_reset{e};
-  e.prebin.want = e.prebin.done = false;
-  if (e.latency_prebin && e.latency_fused && small && n_forests == 2 && ss == 0) {
-    int fm[2], k = 0;
-    bool lstm = false, others = false;
-    for (int m = 0; m < M; ++m) {
-      if (present && !present[m]) continue;
-      if (slots[m] == FD_SLOT_LSTM) lstm = true;
-      else if (slots[m] >= 0 && slots[m] < fd::kMaxSlots && k < 2) fm[k++] = m;
-      else others = true;
-    }
-    if (lstm && !others && k == 2) {
-      const fd::PackedForest& pa = e.forests[slots[fm[0]]];
-      const fd::PackedForest& pb = e.forests[slots[fm[1]]];
-      if (pa.loaded && pb.loaded) fd::forest_pair_prebin(e, pa, pb, dX, n, ld);
-    }
-  }
-  for (int m = 0; m < M; ++m) {  // the LSTM first, so it overlaps the forests
-    if ((present && !present[m]) || slots[m] != FD_SLOT_LSTM) continue;
-    FD_REQUIRE(d_seq != nullptr, FD_ERR_INVALID_ARG,
-               "the LSTM head needs card-history sequences (fd_score_batch_device with seq_len > 0)");
-    double* col = dMP + (size_t)m * n;
-    if (ss == 0) {
-      fd::launch_lstm(e, e.stream, d_seq, n, T, col, d_seq_desc);
-    } else {
-      fork_aux();
-      fd::launch_lstm(e, e.aux_stream, d_seq, n, T, col, d_seq_desc);
-    }
-    cols[m] = col;
-  }
-  const bool use2 = small && ss == 2, use1 = small && ss == 1;
-  if (use2) {
-    if (!e.aux2_stream) {
-      FD_HIP(hipStreamCreateWithFlags(&e.aux2_stream, hipStreamNonBlocking));
-      FD_HIP(hipEventCreateWithFlags(&e.join2_ev, kStreamEventFlags));
-      if (!e.fork_ev) FD_HIP(hipEventCreateWithFlags(&e.fork_ev, kStreamEventFlags));
-    }
-    FD_HIP(hipEventRecord(e.fork_ev, e.stream));
-    FD_HIP(hipStreamWaitEvent(e.aux2_stream, e.fork_ev, 0));
-  }
-  if (use1) fork_aux();
-  // two forests, one stream: one binning launch for both (fd::launch_forest_pair); when every other present model
-  // is the LSTM head (already queued above), both walks in one launch and both sums + the blend in another
-  // (fd::launch_forest_pair_blend: 3 launches instead of 6)
-  bool paired = false;
-  if (small && n_forests == 2 && (ss == 0 || (e.latency_fused && !use2))) {
-    int fm[2], k = 0;
-    for (int m = 0; m < M && k < 2; ++m)
-      if (!(present && !present[m]) && is_forest(m)) fm[k++] = m;
-    const fd::PackedForest& pa = slot_of(e, slots[fm[0]]);
-    const fd::PackedForest& pb = slot_of(e, slots[fm[1]]);
-    if (pa.loaded && pb.loaded) {
-      double* ca = dMP + (size_t)fm[0] * n;
-      double* cb = dMP + (size_t)fm[1] * n;
-      bool others_lstm = true;
-      for (int m = 0; m < M; ++m)
-        if (!(present && !present[m]) && m != fm[0] && m != fm[1] && slots[m] != FD_SLOT_LSTM) others_lstm = false;
-      if (others_lstm && e.latency_fused) {
-        const double* pc[FD_MAX_MODELS] = {};
-        int q = 0, pos_a = -1, pos_b = -1;
-        for (int m = 0; m < M; ++m) {
-          if (present && !present[m]) continue;
-          if (m == fm[0]) pos_a = q;
-          if (m == fm[1]) pos_b = q;
-          pc[q++] = m == fm[0] ? ca : m == fm[1] ? cb : cols[m];
-        }
-        // the LSTM head on the side stream (small_streams 1): the blend launch waits for it
-        hipEvent_t lstm_done = nullptr;
-        if (aux_forked) {
-          FD_HIP(hipEventRecord(e.join_ev, e.aux_stream));
-          lstm_done = e.join_ev;
-        }
-        if (fd::launch_forest_pair_blend(e, pa, pb, dX, n, ld, fd::blend_consts(p, present), pc, pos_a, pos_b, dfp,
-                                         dconf, ddec, drisk, lstm_done))
-          return false;
-      }
-      if (ss == 0) {  // (with side streams the per-forest launches below)
-        paired = fd::launch_forest_pair(e, pa, pb, dX, n, ld, ca, cb);
-        if (paired) {
-          cols[fm[0]] = ca;
-          cols[fm[1]] = cb;
-        }
-      }
-    }
-  }
-  int forests_seen = 0;
-  for (int m = 0; m < M; ++m) {
-    if ((present && !present[m]) || slots[m] == FD_SLOT_LSTM) continue;
-    if (paired && is_forest(m)) continue;
-    double* col = dMP + (size_t)m * n;
-    if (slots[m] == FD_SLOT_MLP) {
-      fd::launch_mlp(e, e.stream, dX, n, ld, col);
-      cols[m] = col;
-    } else if (slots[m] >= 0) {
-      const fd::PackedForest& pf = slot_of(e, slots[m]);
-      FD_REQUIRE(pf.loaded, FD_ERR_NOT_LOADED, "Model in slot " + std::to_string(slots[m]) + " not loaded");
-      const bool side = small && forests_seen++ > 0;
-      const hipStream_t st = side && use2 ? e.aux2_stream : side && use1 ? e.aux_stream : nullptr;
-      fd::launch_forest(e, pf, dX, n, ld, col, nullptr, nullptr, st);
-      cols[m] = col;
-    } else {
-      FD_REQUIRE(ext && ext[m], FD_ERR_INVALID_ARG, "model without slot needs an external probability column");
-      if (ext[m] != col)
-        FD_HIP(hipMemcpyAsync(col, ext[m], (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, e.stream));
-      cols[m] = col;
-    }
-  }
-  if (aux_forked) {
-    FD_HIP(hipEventRecord(e.join_ev, e.aux_stream));
-    FD_HIP(hipStreamWaitEvent(e.stream, e.join_ev, 0));
-  }
-  if (use2) {
-    FD_HIP(hipEventRecord(e.join2_ev, e.aux2_stream));
-    FD_HIP(hipStreamWaitEvent(e.stream, e.join2_ev, 0));
-  }
-  fd::launch_blend(e, p, n, cols, present, dfp, dconf, ddec, drisk);
-  return false;
-}
-
-// fd_ab_score_matrix_*: score_matrix with one model set per variant (device pointers, on e.stream). The batch is
-// assigned and partitioned, the two counts are read back (they size the launches: the one wait), then rows and
-// external columns are gathered into partition order, each variant with rows is scored by score_matrix as a batch of
-// its own, and the results are scattered back to arrival order.
-static void ab_score_matrix(Engine& e, int id, const fd_ab_model_set& c, const fd_ab_model_set& t, const float* dX,
-                            const uint64_t* d_keys, int64_t n, int32_t ld, uint8_t* d_variant, double* dMP,
-                            double* dfp, double* dconf, uint8_t* ddec, uint8_t* drisk) {
-  fd::ab_test(e, id);
-  const fd_ab_model_set* set[2] = {&c, &t};
-  for (const fd_ab_model_set* s : set) {
-    FD_REQUIRE(s->params && s->slots, FD_ERR_INVALID_ARG, "null blend params / slots");
-    FD_REQUIRE(s->params->n_models > 0 && s->params->n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG,
-               "n_models out of range");
-  }
-  FD_REQUIRE(n >= 0 && n < (1ll << 31) && ld > 0, FD_ERR_INVALID_ARG, "bad batch size / row stride");
-  if (n == 0) return;
-  FD_REQUIRE(dX && d_keys && dfp, FD_ERR_INVALID_ARG, "null X / keys / fraud_prob");
-  auto external = [](const fd_ab_model_set& s, int m) {
-    return s.slots[m] < 0 && !(s.present && !s.present[m]);
-  };
-  auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t nn = (size_t)n;
-  // before the counts are known: the index, the two counts, and the variant column when the caller wants none
-  const size_t o_cnt = pad(nn * sizeof(int32_t)), o_var = o_cnt + 256;
-  e.ab.index.ensure(o_var + (d_variant ? 0 : pad(nn)));
-  char* b0 = e.ab.index.as<char>();
-  int32_t* idx = reinterpret_cast<int32_t*>(b0);
-  int64_t* d_counts = reinterpret_cast<int64_t*>(b0 + o_cnt);
-  if (!d_variant) d_variant = reinterpret_cast<uint8_t*>(b0 + o_var);
-  fd::ab_assign(e, id, d_keys, n, d_variant);
-  fd::ab_partition(e, d_variant, n, idx, d_counts);
-  fd::AbScatter sc{};
-  FD_HIP(hipMemcpyAsync(sc.count, d_counts, sizeof(sc.count), hipMemcpyDeviceToHost, e.stream));
-  FD_HIP(hipStreamSynchronize(e.stream));
-  FD_REQUIRE(sc.count[0] >= 0 && sc.count[1] >= 0 && sc.count[0] + sc.count[1] == n, FD_ERR_HIP,
-             "internal: A/B partition counts do not add up");
-  // the batch in partition order, in its own buffer (the index above stays where it is)
-  size_t total = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = total;
-    total += pad(bytes);
-    return at;
-  };
-  const size_t o_x = take(nn * ld * sizeof(float)), o_fp = take(nn * 8), o_conf = take(nn * 8), o_dec = take(nn),
-               o_risk = take(nn);
-  size_t o_mp[2] = {}, o_ext[2][FD_MAX_MODELS] = {};
-  for (int v = 0; v < 2; ++v) {
-    sc.models[v] = set[v]->params->n_models;
-    if (dMP) o_mp[v] = take((size_t)sc.models[v] * sc.count[v] * 8);
-    for (int m = 0; m < sc.models[v]; ++m)
-      if (sc.count[v] && external(*set[v], m)) {
-        FD_REQUIRE(set[v]->ext_probs && set[v]->ext_probs[m], FD_ERR_INVALID_ARG,
-                   "model without slot needs an external probability column");
-        o_ext[v][m] = take((size_t)sc.count[v] * 8);
-      }
-  }
-  e.ab.rows.ensure(total);
-  char* b = e.ab.rows.as<char>();
-  float* Xp = reinterpret_cast<float*>(b + o_x);
-  double *p_fp = reinterpret_cast<double*>(b + o_fp), *p_conf = reinterpret_cast<double*>(b + o_conf);
-  uint8_t *p_dec = reinterpret_cast<uint8_t*>(b + o_dec), *p_risk = reinterpret_cast<uint8_t*>(b + o_risk);
-  fd::ab_gather_rows(e, dX, idx, n, ld, Xp);
-  for (int v = 0; v < 2; ++v) {
-    const int64_t first = v ? sc.count[0] : 0, cnt = sc.count[v];
-    if (cnt == 0) continue;
-    const double* ext[FD_MAX_MODELS] = {};
-    for (int m = 0; m < sc.models[v]; ++m)
-      if (external(*set[v], m)) {
-        double* col = reinterpret_cast<double*>(b + o_ext[v][m]);
-        fd::ab_gather_column(e, set[v]->ext_probs[m], idx + first, cnt, col);
-        ext[m] = col;
-      }
-    double* mp = dMP ? reinterpret_cast<double*>(b + o_mp[v]) : nullptr;
-    sc.p_mp[v] = mp;
-    score_matrix(e, *set[v]->params, set[v]->slots, ext, set[v]->present, Xp + first * ld, cnt, ld, mp, p_fp + first,
-                 dconf ? p_conf + first : nullptr, ddec ? p_dec + first : nullptr, drisk ? p_risk + first : nullptr);
-  }
-  sc.idx = idx;
-  sc.n = n;
-  sc.m_max = std::max(sc.models[0], sc.models[1]);
-  sc.p_fp = p_fp;
-  sc.p_conf = p_conf;
-  sc.p_dec = p_dec;
-  sc.p_risk = p_risk;
-  sc.fp = dfp;
-  sc.conf = dconf;
-  sc.dec = ddec;
-  sc.risk = drisk;
-  sc.mp = dMP;
-  fd::ab_scatter_results(e, sc);
-}
-
-// engine scratch for the fused path's LSTM input sequences, when a present model is the LSTM head
-static float* lstm_seq_buffer(Engine& e, const fd_blend_params& p, const int32_t* slots, const uint8_t* present,
-                              int64_t n) {
-  bool want = false;
-  for (int m = 0; m < p.n_models && m < FD_MAX_MODELS; ++m)
-    want = want || (slots && slots[m] == FD_SLOT_LSTM && !(present && !present[m]));
-  if (!want) return nullptr;
-  FD_REQUIRE(e.state.ready && e.state.S > 0, FD_ERR_INVALID_ARG,
-             "the LSTM head needs card history: fd_state_params.seq_len > 0");
-  e.seq_buf.ensure((size_t)n * e.state.S * fd::kSeqInput * sizeof(float));
-  return e.seq_buf.as<float>();
-}
+using fd::ModelSet;
+using fd::ScoreOut;
+using fd::slot_of;
 
 extern "C" {
 
@@ -422,8 +141,8 @@ int fd_engine_destroy(fd_engine* eng) {
   if (e.comm.aborted) {  // an aborted exchange: every stream gets a bounded wait; one that never drains leaks the engine
     bool ok = fd::comm_sync_stream(e, e.comm.x_fwd);
     ok = fd::comm_sync_stream(e, e.stream) && ok;
-    for (hipStream_t st : e.pipe_stream) ok = fd::comm_sync_stream(e, st) && ok;
-    ok = fd::comm_sync_stream(e, e.pipe_slot_stream) && ok;
+    for (hipStream_t st : e.pipe.stream) ok = fd::comm_sync_stream(e, st) && ok;
+    ok = fd::comm_sync_stream(e, e.pipe.slot_stream) && ok;
     FD_REQUIRE(ok, FD_ERR_HIP, "engine leaked: streams still busy " + std::to_string(e.comm.timeout_ms) +
                                    " ms after the communicators were aborted (" + e.comm.abort_reason + ")");
   }
@@ -452,43 +171,12 @@ int fd_engine_destroy(fd_engine* eng) {
   for (auto* b : {&e.route_blk, &e.route_blk_stream, &e.route_out, &e.route_err, &e.seq_buf, &e.seq_desc, &e.lstm.wpk, &e.lstm.wpk4, &e.lstm.bias,
                   &e.lstm.wout, &e.lstm.bout, &e.state.seq, &e.mlp.blob})
     b->release();
-  if (e.aux_stream) {
-    (void)hipStreamSynchronize(e.aux_stream);
-    (void)hipStreamDestroy(e.aux_stream);
-    (void)hipEventDestroy(e.fork_ev);
-    (void)hipEventDestroy(e.join_ev);
-  }
-  if (e.aux2_stream) {
-    (void)hipStreamSynchronize(e.aux2_stream);
-    (void)hipStreamDestroy(e.aux2_stream);
-    (void)hipEventDestroy(e.join2_ev);
-  }
+  e.side.release();
   try {
     fd::comm_destroy(e);
   } catch (...) {
   }
-  for (hipStream_t st : e.pipe_stream)
-    if (st) {
-      (void)hipStreamSynchronize(st);
-      (void)hipStreamDestroy(st);
-    }
-  if (e.pipe_slot_stream) {
-    (void)hipStreamSynchronize(e.pipe_slot_stream);
-    (void)hipStreamDestroy(e.pipe_slot_stream);
-  }
-  if (e.pipe_entry_ev) (void)hipEventDestroy(e.pipe_entry_ev);
-  for (int k = 0; k < Engine::kPipeSlots; ++k) {
-    if (e.pipe_slot_ev[k]) (void)hipEventDestroy(e.pipe_slot_ev[k]);
-    if (e.pipe_feat_ev[k]) (void)hipEventDestroy(e.pipe_feat_ev[k]);
-    if (e.pipe_copy_ev[k]) (void)hipEventDestroy(e.pipe_copy_ev[k]);
-    e.pipe_vec[k].release();
-    e.pipe_out[k].release();
-    e.pipe_seq[k].release();
-  }
-  for (int k = 0; k < Engine::kSplitRing; ++k) {
-    if (e.pipe_done_ev[k]) (void)hipEventDestroy(e.pipe_done_ev[k]);
-    e.pipe_split[k].release();
-  }
+  e.pipe.release();
   for (auto* b : {&e.state.uext, &e.state.mext, &e.state.vocab, &e.feat_ext}) b->release();
   for (auto& P1 : e.ens1)
     for (auto* b : {&P1.nodes[0], &P1.nodes[1], &P1.thr}) b->release();
@@ -521,8 +209,7 @@ int fd_engine_destroy(fd_engine* eng) {
 // the new engine stream inherits the order of the old one over pipelined batches: their scoring is complete
 // before anything queued on it (fd_score_batch_pipelined's outputs stay ordered on the engine stream)
 static void rebind_stream(Engine& e, hipStream_t s) {
-  for (int k = 0; k < Engine::kDoneRing; ++k)
-    if (e.pipe_done_live[k] && s != e.stream) FD_HIP(hipStreamWaitEvent(s, e.pipe_done_ev[k], 0));
+  if (s != e.stream) e.pipe.order_after_scoring(s);
   e.stream = s;
 }
 
@@ -549,19 +236,16 @@ int fd_engine_sync(fd_engine* eng) {
   if (e.comm.aborted) {  // streams behind an aborted exchange: bounded waits, then the abort's reason
     bool ok = fd::comm_sync_stream(e, e.comm.x_fwd);
     ok = fd::comm_sync_stream(e, e.stream) && ok;
-    for (hipStream_t st : e.pipe_stream) ok = fd::comm_sync_stream(e, st) && ok;
-    // the slot pass and the aux streams can be queued behind an aborted inbox event too (as fd_engine_destroy)
-    for (hipStream_t st : {e.pipe_slot_stream, e.aux_stream, e.aux2_stream}) ok = fd::comm_sync_stream(e, st) && ok;
+    for (hipStream_t st : e.pipe.stream) ok = fd::comm_sync_stream(e, st) && ok;
+    // the slot pass and the side streams can be queued behind an aborted inbox event too (as fd_engine_destroy)
+    for (hipStream_t st : {e.pipe.slot_stream, e.side.st[0], e.side.st[1]}) ok = fd::comm_sync_stream(e, st) && ok;
     FD_REQUIRE(ok, FD_ERR_HIP, "streams still busy " + std::to_string(e.comm.timeout_ms) +
                                    " ms after the communicators were aborted (" + e.comm.abort_reason + ")");
   }
   FD_HIP(hipStreamSynchronize(e.stream));
   if (e.comm.x_fwd) FD_HIP(hipStreamSynchronize(e.comm.x_fwd));
-  for (hipStream_t st : e.pipe_stream)
+  for (hipStream_t st : {e.pipe.stream[0], e.pipe.stream[1], e.pipe.slot_stream, e.side.st[0], e.side.st[1]})
     if (st) FD_HIP(hipStreamSynchronize(st));
-  if (e.pipe_slot_stream) FD_HIP(hipStreamSynchronize(e.pipe_slot_stream));
-  if (e.aux_stream) FD_HIP(hipStreamSynchronize(e.aux_stream));
-  if (e.aux2_stream) FD_HIP(hipStreamSynchronize(e.aux2_stream));
   fd::route_check(e);
   FD_API_END
 }
@@ -581,7 +265,7 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
   FD_REQUIRE(key && value, FD_ERR_INVALID_ARG, "null key/value");
   const std::string k(key);
   if (k == "pipelined_batches") {  // fd_score_batch_pipelined / fd_score_records_pipelined batches so far
-    *value = (int64_t)e.pipe_iter_total;
+    *value = (int64_t)e.pipe.iter_total;
   } else if (k == "ensemble_single_launches") {  // fd_forest_predict batches scored by the fused kernel over one
     // forest (probabilities, optionally raw scores; no leaf ids): config 2's timed kernel, ensemble_kernel<8,2>
     *value = (int64_t)e.ens_single_total;
@@ -623,20 +307,20 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
   } else if (k == "latency_prebinned_batches") {  // latency pair launches that used the feature kernel's bins
     *value = (int64_t)e.prebin_total;
   } else if (k == "pipelined_split_batches") {  // of the compact ones: split rows (compact_vectors 2)
-    *value = (int64_t)e.pipe_split_total;
+    *value = (int64_t)e.pipe.split_total;
   } else if (k == "pipelined_compact_batches") {  // of those: scored by the fused kernel from the compact 64-B
     // rows (no vectors requested), the variant the config-3/4 bench times
-    *value = (int64_t)e.pipe_compact_total;
+    *value = (int64_t)e.pipe.compact_total;
   } else if (k == "pipelined_host_ns") {  // host nanoseconds inside fd_score_batch_pipelined (HIP launches, event
     // records and waits of the pipelined step)
-    *value = (int64_t)e.pipe_host_ns;
+    *value = (int64_t)e.pipe.host_ns;
   } else if (k == "pipelined_slot_stream_batches") {  // of those: the slot pass on its own stream (slot_stream)
-    *value = (int64_t)e.pipe_slot_stream_total;
+    *value = (int64_t)e.pipe.slot_stream_total;
   } else if (k == "window_saturated") {  // sliding windows: transactions whose 24 h window held K prior events
     // (its count may be truncated at the ring capacity); synchronises the engine's streams
     FD_REQUIRE(e.state.ready, FD_ERR_NOT_LOADED, "card state not initialised (fd_state_init)");
     FD_HIP(hipStreamSynchronize(e.stream));
-    for (hipStream_t st : e.pipe_stream)
+    for (hipStream_t st : e.pipe.stream)
       if (st) FD_HIP(hipStreamSynchronize(st));
     unsigned long long v = 0;
     FD_HIP(hipMemcpy(&v, e.state.sat.ptr, 8, hipMemcpyDeviceToHost));
@@ -710,12 +394,12 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value) {
     e.latency_fused = value != 0;
   } else if (k == "pipeline_lean") {  // fd_score_batch_pipelined's bucket pass: 1 (default) lean + deferred
     FD_REQUIRE(value == 0 || value == 1, FD_ERR_INVALID_ARG, "pipeline_lean must be 0 or 1");
-    e.pipe_lean = value != 0;
+    e.pipe.lean = value != 0;
   } else if (k == "pipeline_gather") {  // fd_score_batch_pipelined, batches of <= 4096 transactions (slot_gather on,
     // no slot stream): 1 (default) the gather bucket kernel (card slots found inside it, one feature launch), 0 the
     // slot + lean bucket pair of the large batches
     FD_REQUIRE(value == 0 || value == 1, FD_ERR_INVALID_ARG, "pipeline_gather must be 0 or 1");
-    e.pipe_gather = value != 0;
+    e.pipe.gather = value != 0;
   } else if (k == "latency_prebin") {  // latency batches with the LSTM head: the XGBoost + IsolationForest pair's
     // tree-split binning in the LSTM launch: 3 (default) inside the LSTM's own workgroups (a lifting level per
     // recurrence step; 2 where a thread would have more than two searches), 2 in extra workgroups after the LSTM's
@@ -745,7 +429,7 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value) {
     // forests) then sat in front of batch i+1's feature kernels in one queue — the native sharded step measured
     // 0.137 ms per 64 k batch at 0, 0.093 at 2 / 3 (the direct step 0.089 either way).
     FD_REQUIRE(value >= 0 && value <= 3, FD_ERR_INVALID_ARG, "stream_priority must be in 0..3");
-    FD_REQUIRE(!e.pipe_stream[0] && !e.comm.x_fwd, FD_ERR_INVALID_ARG,
+    FD_REQUIRE(!e.pipe.stream[0] && !e.comm.x_fwd, FD_ERR_INVALID_ARG,
                "stream_priority: set before the first pipelined call and fd_comm_init");
     e.stream_prio = (int)value;
   } else if (k == "bucket_keys") {  // feature bucket pass: transactions per bucket workgroup, 0 auto (8 up to
@@ -769,9 +453,9 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value) {
     // priority, 2 low; 0 on pipe_stream[i & 1] behind batch i-2's fused kernel; -1 auto by the card table's size),
     // set before the first pipelined call
     FD_REQUIRE(value >= -1 && value <= 2, FD_ERR_INVALID_ARG, "slot_stream must be -1, 0, 1 or 2");
-    FD_REQUIRE(!e.pipe_slot_stream || (int)value == e.pipe_slot_mode, FD_ERR_INVALID_ARG,
+    FD_REQUIRE(!e.pipe.slot_stream || (int)value == e.pipe.slot_mode, FD_ERR_INVALID_ARG,
                "slot_stream: set before the first pipelined call");
-    e.pipe_slot_mode = (int)value;
+    e.pipe.slot_mode = (int)value;
   } else if (k == "slot_prio") {  // pipelined stream: 1 the slot kernel's waves issue at priority 2, 0 (default) not
     FD_REQUIRE(value == 0 || value == 1, FD_ERR_INVALID_ARG, "slot_prio must be 0 or 1");
     e.state.slot_prio = value != 0;
@@ -1701,8 +1385,8 @@ int fd_score_matrix_device(fd_engine* eng, const fd_blend_params* params, const 
   FD_ENGINE_LOCK(eng);
   Engine& e = E(eng);
   FD_REQUIRE(params && d_X && ld > 0 && n >= 0, FD_ERR_INVALID_ARG, "bad arguments");
-  score_matrix(e, *params, slots, ext_probs, present, d_X, n, ld, d_model_probs, d_fraud_prob, d_confidence,
-               d_decision, d_risk);
+  fd::score_matrix(e, ModelSet(params, slots, ext_probs, present), fd::ScoreRows(d_X, n, ld),
+                   ScoreOut{d_model_probs, d_fraud_prob, d_confidence, d_decision, d_risk});
   FD_API_END
 }
 
@@ -1714,54 +1398,29 @@ int fd_score_matrix_host(fd_engine* eng, const fd_blend_params* params, const in
   FD_ENGINE_LOCK(eng);
   Engine& e = E(eng);
   FD_REQUIRE(params && slots && X && fraud_prob && ld > 0 && n >= 0, FD_ERR_INVALID_ARG, "bad arguments");
-  FD_REQUIRE(params->n_models > 0 && params->n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, "n_models out of range");
+  fd::require_model_count(*params, "n_models out of range");
   if (n == 0) return FD_OK;
   const int M = params->n_models;
+  const ModelSet host(params, slots, ext_probs, present);
   Stage st(e);
-  const float* dX;
+  fd::ScoreRows rows(nullptr, n, ld);
   const double* dext[FD_MAX_MODELS] = {};
-  double *dMP, *dfp, *dconf;
-  uint8_t *ddec, *drisk;
-  st.in(dX, X, (size_t)n * ld);
+  ScoreOut out;
+  st.in(rows.X, X, (size_t)n * ld);
   for (int m = 0; m < M; ++m) {  // the external columns; score_matrix copies each into its place in the matrix
-    if (slots[m] >= 0 || (present && !present[m])) continue;
+    if (!host.external(m)) continue;
     FD_REQUIRE(ext_probs && ext_probs[m], FD_ERR_INVALID_ARG, "model without slot needs an external probability column");
     st.in(dext[m], ext_probs[m], (size_t)n);
   }
-  st.out(dMP, model_probs, (size_t)n * M);  // absent: score_matrix keeps the matrix in its own scratch
-  st.out(dfp, fraud_prob, (size_t)n);
-  st.out(dconf, confidence, (size_t)n);
-  st.out(ddec, decision, (size_t)n);
-  st.out(drisk, risk, (size_t)n);
+  st.out(out.mp, model_probs, (size_t)n * M);  // absent: score_matrix keeps the matrix in its own scratch
+  st.out(out.fp, fraud_prob, (size_t)n);
+  st.out(out.conf, confidence, (size_t)n);
+  st.out(out.dec, decision, (size_t)n);
+  st.out(out.risk, risk, (size_t)n);
   st.upload();
-  score_matrix(e, *params, slots, dext, present, dX, n, ld, dMP, dfp, dconf, ddec, drisk);
+  fd::score_matrix(e, ModelSet(params, slots, dext, present), rows, out);
   st.download();
   FD_API_END
-}
-
-static void score_batch_body(Engine& e, const fd_blend_params& p, const int32_t* slots, const double* const* ext,
-                             const uint8_t* present, const fd_txn_batch& t, int64_t n, float* d_vectors,
-                             double* dMP, double* dfp, double* dconf, uint8_t* ddec, uint8_t* drisk) {
-  float* vec = d_vectors;
-  if (!vec) {
-    e.feat_vec.ensure((size_t)n * FD_VECTOR_WIDTH * 4);
-    vec = e.feat_vec.as<float>();
-  }
-  float* seq = lstm_seq_buffer(e, p, slots, present, n);
-  // latency batches: the LSTM (4-row kernel) reads each card's last transaction's sequence from the history ring,
-  // which nothing rewrites before it runs (the next batch's features follow on this stream); the feature kernel
-  // writes only the other rows
-  unsigned long long* desc = nullptr;
-  if (seq && e.seq_ring_lstm && n < 4096 && (e.lstm_rows == 0 || e.lstm_rows == 4)) {
-    e.seq_desc.ensure((size_t)n * sizeof(unsigned long long));
-    desc = e.seq_desc.as<unsigned long long>();
-    // a transaction whose card probe fails (table full) gets no descriptor from the feature kernel: the gather
-    // kernel writes kSeqMaterialized for it; the slot-kernel path starts from all-materialized (bit 63 set)
-    if (!e.state.slot_gather) FD_HIP(hipMemsetAsync(desc, 0xff, (size_t)n * sizeof(unsigned long long), e.stream));
-  }
-  fd::launch_features(e, t, n, vec, nullptr, seq, nullptr, nullptr, false, 0, nullptr, false, desc);
-  score_matrix(e, p, slots, ext, present, vec, n, FD_VECTOR_WIDTH, dMP, dfp, dconf, ddec, drisk, seq, e.state.S,
-               nullptr, nullptr, false, desc);
 }
 
 int fd_score_batch_device(fd_engine* eng, const fd_blend_params* params, const int32_t* slots,
@@ -1774,195 +1433,9 @@ int fd_score_batch_device(fd_engine* eng, const fd_blend_params* params, const i
   FD_REQUIRE(params && txns && n >= 0, FD_ERR_INVALID_ARG, "bad arguments");
   if (n == 0) return FD_OK;
   FD_REQUIRE(slots != nullptr && d_fraud_prob != nullptr, FD_ERR_INVALID_ARG, "null slots/output");
-  score_batch_body(e, *params, slots, ext_probs, present, *txns, n, d_vectors, d_model_probs, d_fraud_prob,
-                   d_confidence, d_decision, d_risk);
+  fd::score_batch(e, ModelSet(params, slots, ext_probs, present), *txns, n, d_vectors,
+                  ScoreOut{d_model_probs, d_fraud_prob, d_confidence, d_decision, d_risk});
   FD_API_END
-}
-
-// fd_score_batch_pipelined's outputs: engine staging -> the caller's buffers, on the engine stream (one thread per
-// transaction; null destinations are skipped); result records (routed batches) as 8-byte words
-__global__ void __launch_bounds__(256)
-pipe_out_copy_kernel(const double* __restrict__ fp, const double* __restrict__ conf, const uint8_t* __restrict__ dec,
-                     const uint8_t* __restrict__ risk, const double* __restrict__ mp, int n_mp, int64_t n,
-                     double* __restrict__ o_fp, double* __restrict__ o_conf, uint8_t* __restrict__ o_dec,
-                     uint8_t* __restrict__ o_risk, double* __restrict__ o_mp, const float4* __restrict__ vec,
-                     float4* __restrict__ o_vec, const uint64_t* __restrict__ res, uint64_t* __restrict__ o_res) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (o_vec) {  // the vectors: 16 float4 per row, one float4 per thread over the whole grid
-    const int64_t total = n * (FD_VECTOR_WIDTH / 4);
-    for (int64_t q = i; q < total; q += stride) o_vec[q] = vec[q];
-  }
-  if (o_res) {
-    const int64_t total = n * (int64_t)(sizeof(fd::ResultRecord) / 8);
-    for (int64_t q = i; q < total; q += stride) o_res[q] = res[q];
-  }
-  if (i >= n) return;
-  if (o_fp) o_fp[i] = fp[i];
-  if (o_conf) o_conf[i] = conf[i];
-  if (o_dec) o_dec[i] = dec[i];
-  if (o_risk) o_risk[i] = risk[i];
-  for (int m = 0; m < n_mp; ++m) o_mp[(size_t)m * n + i] = mp[(size_t)m * n + i];
-}
-
-// One micro-batch of the pipelined stream: transaction columns (txns) or routed 48-B records (records, whose scores
-// leave as 24-B result records in d_results). Shared by fd_score_batch_pipelined and fd_score_records_pipelined.
-static void pipe_step(Engine& e, const fd_blend_params* params, const int32_t* slots, const double* const* ext_probs,
-                      const uint8_t* present, const fd_txn_batch* txns, const void* records, int64_t n,
-                      float* d_vectors, double* d_model_probs, double* d_fraud_prob, double* d_confidence,
-                      uint8_t* d_decision, uint8_t* d_risk, void* d_results, void* input_ready,
-                      bool results_in_place = false) {
-  for (int k = 0; k < 2; ++k)
-    if (!e.pipe_stream[k]) e.pipe_stream[k] = fd::make_stream(e.stream_prio >= 1 ? 1 : 0);
-  if (e.pipe_slot_mode < 0)  // auto: where the feature chain outlasts the fused kernel (random card traffic over a
-    // large table), not where an earlier slot pass only adds contention beside it
-    e.pipe_slot_mode = (e.state.ready && e.state.cap >= (1ll << 26)) ? 2 : 0;
-  if (e.pipe_slot_mode && !e.pipe_slot_stream) {
-    e.pipe_slot_stream = fd::make_stream(e.pipe_slot_mode == 1 ? 1 : -1);
-    for (int k = 0; k < Engine::kPipeSlots; ++k) FD_HIP(hipEventCreateWithFlags(&e.pipe_slot_ev[k], kStreamEventFlags));
-  }
-  if (!e.pipe_entry_ev) {
-    FD_HIP(hipEventCreateWithFlags(&e.pipe_entry_ev, kStreamEventFlags));
-    for (int k = 0; k < Engine::kPipeSlots; ++k) {
-      FD_HIP(hipEventCreateWithFlags(&e.pipe_feat_ev[k], kStreamEventFlags));
-      FD_HIP(hipEventCreateWithFlags(&e.pipe_copy_ev[k], kStreamEventFlags));
-    }
-    for (int k = 0; k < Engine::kDoneRing; ++k) FD_HIP(hipEventCreateWithFlags(&e.pipe_done_ev[k], kStreamEventFlags));
-  }
-  // Batch i: buffer slot s = i mod 2, its features and its scoring on Sc = pipe_stream[i & 1] (Sf: the same
-  // stream). Card-state order: batch i's bucket pass after batch i-1's (an event). Buffer s is free once batch
-  // i-2's scoring is done (the same queue). Outputs: the engine stream waits for batch i's scoring. (Measured and
-  // dropped: one feature stream for every batch + two scoring streams, ring of three buffers — the third stream
-  // shares a hardware queue with a scoring stream: 567 vs 742 M txn/s)
-  constexpr int nbuf = 2;
-  const int s = (int)(e.pipe_iter % (unsigned long long)nbuf);
-  const int prev = s ^ 1;
-  hipStream_t Sc = e.pipe_stream[e.pipe_iter & 1];
-  hipStream_t Sf = Sc;
-  // option slot_stream: the slot pass on Ss, after what it reads (the entry order, the inputs) and batch i-2's
-  // bucket pass (scratch set s: its fill counts and keys are consumed and reset there); feat_slot_kernel only
-  // finds / inserts card keys, which the bucket passes of earlier batches never change
-  hipStream_t Ss = e.pipe_slot_stream;
-  if (e.pipe_dirty) {  // work queued on e.stream by other calls (state loads, snapshots, ...) comes first
-    FD_HIP(hipEventRecord(e.pipe_entry_ev, e.stream));
-    FD_HIP(hipStreamWaitEvent(Sf, e.pipe_entry_ev, 0));
-    if (Ss) FD_HIP(hipStreamWaitEvent(Ss, e.pipe_entry_ev, 0));
-    e.pipe_dirty = false;
-  }
-  if (input_ready) FD_HIP(hipStreamWaitEvent(Sf, static_cast<hipEvent_t>(input_ready), 0));
-  if (Ss && input_ready) FD_HIP(hipStreamWaitEvent(Ss, static_cast<hipEvent_t>(input_ready), 0));
-  if (Ss && e.pipe_feat_live[s]) FD_HIP(hipStreamWaitEvent(Ss, e.pipe_feat_ev[s], 0));
-  // the slot's vectors are rewritten below: after batch i-nbuf's output copy if that one read them
-  if (e.pipe_copy_live[s] && e.pipe_copy_vec[s]) FD_HIP(hipStreamWaitEvent(Sf, e.pipe_copy_ev[s], 0));
-  // mode 1: the slot pass (scratch set s & 1, untouched by batch i-1) runs at once; the bucket pass waits for
-  // batch i-1's card updates
-  hipEvent_t before_buckets = e.pipe_feat_live[prev] ? e.pipe_feat_ev[prev] : nullptr;
-  // the fused kernel alone reads the vectors and nobody asked for them: the compact form (64 instead of 256 B per
-  // transaction written here and read by the ensemble kernel, fd_internal.h kCompactSlot), or split rows
-  // (compact 2: the slot pass writes the card-independent half, the bucket pass reads 32-B instead of 64-B prep
-  // records; the lean bucket pass only, and not with LSTM history in the card state)
-  int compact = (e.compact_vectors && d_vectors == nullptr && fd::ensemble_applies(e, *params, slots, present, n))
-                    ? e.compact_vectors : 0;
-  float* vec = nullptr;
-  const int sr = (int)(e.pipe_iter % (unsigned long long)Engine::kSplitRing);  // split rows: this batch's ring buffer
-  float* seq = nullptr;
-  bool want_seq = false;
-  for (int m = 0; m < params->n_models && m < FD_MAX_MODELS; ++m)
-    want_seq = want_seq || (slots && slots[m] == FD_SLOT_LSTM && !(present && !present[m]));
-  if (want_seq) {
-    FD_REQUIRE(e.state.ready && e.state.S > 0, FD_ERR_INVALID_ARG,
-               "the LSTM head needs card history: fd_state_params.seq_len > 0");
-    e.pipe_seq[s].ensure((size_t)n * e.state.S * fd::kSeqInput * sizeof(float));
-    seq = e.pipe_seq[s].as<float>();
-  }
-  // latency-sized batches: the gather kernel (slot pass inside the bucket launch) instead of the slot + lean pair,
-  // whose two launches cost 39 us per 1 k batch against its 18; it waits for batch i-1's card updates
-  // (before_buckets) like the lean pass
-  const bool lean = e.pipe_lean && !(e.pipe_gather && e.state.slot_gather && n <= fd::kGatherBatchMax && !Ss);
-  if (compact == 2 && (!lean || want_seq || e.state.S > 0)) compact = 1;
-  if (compact == 2) {  // RowA | RowB in the ring; the slot pass (which writes RowA) after the last fused kernel that
-    // read this buffer — on the slot stream that is an explicit wait, on the batch's own stream the stream order
-    e.pipe_split[sr].ensure((size_t)n * 64);
-    vec = e.pipe_split[sr].as<float>();
-    if (Ss && e.pipe_done_live[sr]) FD_HIP(hipStreamWaitEvent(Ss, e.pipe_done_ev[sr], 0));  // batch i - 4's
-  } else {  // the 64-wide vectors or compact rows: the slot's own buffer (split-row batches never touch it)
-    e.pipe_vec[s].ensure((size_t)n * FD_VECTOR_WIDTH * 4);
-    vec = e.pipe_vec[s].as<float>();
-  }
-  {
-    struct SlotPass {  // launch_grouped reads these for this call only
-      Engine& e;
-      ~SlotPass() { e.slot_pass_stream = nullptr, e.slot_pass_ev = nullptr; }
-    } slot_pass{e};
-    e.slot_pass_stream = Ss;
-    e.slot_pass_ev = Ss ? e.pipe_slot_ev[s] : nullptr;
-    if (records)
-      fd::launch_features_records(e, records, n, vec, seq, Sf, lean, s, before_buckets, compact);
-    else
-      fd::launch_features(e, *txns, n, vec, nullptr, seq, nullptr, Sf, lean, s, before_buckets, compact);
-  }
-  FD_HIP(hipEventRecord(e.pipe_feat_ev[s], Sf));
-  e.pipe_feat_live[s] = true;
-  // scoring paths other than the fused kernel share engine scratch (per-model columns, tree-split and LSTM
-  // buffers): those batches also wait for the previous batch's scoring
-  const int pr = (sr + Engine::kDoneRing - 1) % Engine::kDoneRing;  // batch i - 1's done event
-  if (e.pipe_done_live[pr] && !compact && !fd::ensemble_applies(e, *params, slots, present, n))
-    FD_HIP(hipStreamWaitEvent(Sc, e.pipe_done_ev[pr], 0));
-  // this slot's output staging: free once batch i-nbuf's copy to its caller (on e.stream) is done. Routed batches
-  // always stage the four columns (the result records are packed from them when the fused kernel does not apply).
-  const int n_mp = d_model_probs ? params->n_models : 0;
-  const size_t n8 = (size_t)n * 8, a8 = ((size_t)n + 7) & ~(size_t)7;
-  // results_in_place (fd_sharded_step: d_results is the engine's own res[q], free by the step's event order, see
-  // ShardComm::res): the scoring writes the result records there, no staging copy; otherwise they are staged and
-  // copied on the engine stream like the columns (a caller's buffer is written only in the engine stream's order)
-  const bool in_place = records && results_in_place;
-  const size_t rbytes = records && !in_place ? (size_t)n * sizeof(fd::ResultRecord) : 0;
-  e.pipe_out[s].ensure((2 + (size_t)n_mp) * n8 + 2 * a8 + rbytes);
-  char* so = e.pipe_out[s].as<char>();
-  double* s_fp = reinterpret_cast<double*>(so);
-  double* s_conf = (d_confidence || records) ? reinterpret_cast<double*>(so + n8) : nullptr;
-  double* s_mp = n_mp ? reinterpret_cast<double*>(so + 2 * n8) : nullptr;
-  uint8_t* s_dec = (d_decision || records) ? reinterpret_cast<uint8_t*>(so + (2 + (size_t)n_mp) * n8) : nullptr;
-  uint8_t* s_risk = (d_risk || records) ? reinterpret_cast<uint8_t*>(so + (2 + (size_t)n_mp) * n8 + a8) : nullptr;
-  auto* s_res = !records ? nullptr
-                         : in_place ? static_cast<fd::ResultRecord*>(d_results)
-                                    : reinterpret_cast<fd::ResultRecord*>(so + (2 + (size_t)n_mp) * n8 + 2 * a8);
-  if (e.pipe_copy_live[s]) FD_HIP(hipStreamWaitEvent(Sc, e.pipe_copy_ev[s], 0));
-  ++e.pipe_iter;
-  ++e.pipe_iter_total;
-  e.pipe_compact_total += compact != 0;
-  e.pipe_split_total += compact == 2;
-  e.pipe_slot_stream_total += Ss != nullptr;
-  {  // the scoring launches go on Sc: score_matrix launches on e.stream
-    struct Swap {
-      Engine& e;
-      hipStream_t saved;
-      ~Swap() { e.stream = saved; }
-    } swap{e, e.stream};
-    e.stream = Sc;
-    const auto* rec = static_cast<const fd::RouteRecord*>(records);
-    if (!score_matrix(e, *params, slots, ext_probs, present, vec, n, FD_VECTOR_WIDTH, s_mp, s_fp, s_conf, s_dec,
-                      s_risk, seq, e.state.S, rec, s_res, compact) &&
-        records)
-      fd::launch_result_pack(e, s_fp, s_conf, s_dec, s_risk, rec, n, s_res);
-  }
-  // (split rows: this event also releases ring buffer sr to batch i + 4's slot pass — no event of its own, which
-  // cost a record per step on the engine stream; recorded on Sc beside the fused kernel it cost 4 % in round 6)
-  FD_HIP(hipEventRecord(e.pipe_done_ev[sr], Sc));
-  e.pipe_done_live[sr] = true;
-  FD_HIP(hipStreamWaitEvent(e.stream, e.pipe_done_ev[sr], 0));
-  if (in_place) {  // nothing to copy: the next use of staging slot s (batch i + 2) is on this batch's stream Sc
-    e.pipe_copy_live[s] = false;
-    return;
-  }
-  hipLaunchKernelGGL(pipe_out_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e.stream, s_fp, s_conf,
-                     s_dec, s_risk, s_mp, n_mp, n, records ? nullptr : d_fraud_prob, d_confidence, d_decision, d_risk,
-                     d_model_probs, reinterpret_cast<const float4*>(vec), reinterpret_cast<float4*>(d_vectors),
-                     reinterpret_cast<const uint64_t*>(s_res), static_cast<uint64_t*>(d_results));
-  FD_HIP(hipGetLastError());
-  FD_HIP(hipEventRecord(e.pipe_copy_ev[s], e.stream));
-  e.pipe_copy_live[s] = true;
-  e.pipe_copy_vec[s] = d_vectors != nullptr;
 }
 
 int fd_score_batch_pipelined(fd_engine* eng, const fd_blend_params* params, const int32_t* slots,
@@ -1975,11 +1448,16 @@ int fd_score_batch_pipelined(fd_engine* eng, const fd_blend_params* params, cons
   FD_REQUIRE(params && txns && n >= 0, FD_ERR_INVALID_ARG, "bad arguments");
   if (n == 0) return FD_OK;
   FD_REQUIRE(d_fraud_prob != nullptr, FD_ERR_INVALID_ARG, "null fraud_prob output");
-  FD_REQUIRE(params->n_models >= 1 && params->n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, "bad n_models");
+  fd::require_model_count(*params, "bad n_models");
+  fd::PipeBatch b;
+  b.txns = txns;
+  b.n = n;
+  b.d_vectors = d_vectors;
+  b.out = ScoreOut{d_model_probs, d_fraud_prob, d_confidence, d_decision, d_risk};
+  b.input_ready = input_ready;
   const auto t0 = std::chrono::steady_clock::now();
-  pipe_step(e, params, slots, ext_probs, present, txns, nullptr, n, d_vectors, d_model_probs, d_fraud_prob,
-            d_confidence, d_decision, d_risk, nullptr, input_ready);
-  e.pipe_host_ns += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(
+  fd::pipe_step(e, ModelSet(params, slots, ext_probs, present), b);
+  e.pipe.host_ns += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(
                         std::chrono::steady_clock::now() - t0).count();
   FD_API_END
 }
@@ -1991,27 +1469,18 @@ int fd_score_records_pipelined(fd_engine* eng, const fd_blend_params* params, co
   FD_ENGINE_LOCK(eng);
   Engine& e = E_quiet(eng);
   FD_REQUIRE(params && slots && n >= 0, FD_ERR_INVALID_ARG, "bad arguments");
-  FD_REQUIRE(params->n_models >= 1 && params->n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, "bad n_models");
-  for (int m = 0; m < params->n_models; ++m)
-    FD_REQUIRE(slots[m] >= 0 || (present && !present[m]), FD_ERR_INVALID_ARG,
-               "routed scoring needs every present model in a forest slot, FD_SLOT_LSTM or FD_SLOT_MLP");
+  fd::require_model_count(*params, "bad n_models");
+  const ModelSet ms(params, slots, nullptr, present);
+  fd::require_all_in_slots(ms);
   if (n == 0) return FD_OK;
   FD_REQUIRE(d_records != nullptr && d_results != nullptr, FD_ERR_INVALID_ARG, "null records / results");
-  pipe_step(e, params, slots, nullptr, present, nullptr, d_records, n, nullptr, nullptr, nullptr, nullptr, nullptr,
-            nullptr, d_results, input_ready);
+  fd::PipeBatch b;
+  b.records = d_records;
+  b.n = n;
+  b.d_results = d_results;
+  b.input_ready = input_ready;
+  fd::pipe_step(e, ms, b);
   FD_API_END
-}
-
-extern "C++" hipStream_t fd::make_stream(int level) {
-  hipStream_t st = nullptr;
-  if (level == 0) {
-    FD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    return st;
-  }
-  int least = 0, greatest = 0;
-  FD_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-  FD_HIP(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, level > 0 ? greatest : least));
-  return st;
 }
 
 // ---------------------------------------------------------------- card-hash sharded step over RCCL (comm.hip)
@@ -2052,69 +1521,14 @@ int fd_sharded_step(fd_engine* eng, const fd_blend_params* params, const int32_t
   FD_REQUIRE(!c.aborted, FD_ERR_HIP, "communicators aborted (" + c.abort_reason + "): fd_comm_destroy, then fd_comm_init");
   FD_REQUIRE(params && slots && txns && n >= 0 && (!next || next_n >= 0), FD_ERR_INVALID_ARG, "bad arguments");
   FD_REQUIRE(!next || next_id != 0, FD_ERR_INVALID_ARG, "a prefetched batch needs a nonzero next_id");
-  FD_REQUIRE(params->n_models >= 1 && params->n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, "bad n_models");
-  for (int m = 0; m < params->n_models; ++m)
-    FD_REQUIRE(slots[m] >= 0 || (present && !present[m]), FD_ERR_INVALID_ARG,
-               "routed scoring needs every present model in a forest slot, FD_SLOT_LSTM or FD_SLOT_MLP");
+  fd::require_model_count(*params, "bad n_models");
+  const ModelSet ms(params, slots, nullptr, present);
+  fd::require_all_in_slots(ms);
   FD_REQUIRE(n == 0 || d_fraud_prob, FD_ERR_INVALID_ARG, "null fraud_prob output");
-  // the prefetched batch is named by its id: batch_id 0 drops a pending prefetch (on every rank alike: its count
-  // exchange completes, its records are never sent); any other id must be the pending one
-  const bool use_pending = batch_id != 0;
-  if (use_pending)
-    FD_REQUIRE(c.pending && batch_id == c.pending_id && n == c.pending_n, FD_ERR_INVALID_ARG,
-               "batch " + std::to_string(batch_id) + " (n " + std::to_string(n) + ") is not the prefetched batch " +
-                   std::to_string(c.pending_id) + " (n " + std::to_string(c.pending_n) +
-                   "): pass its id, or 0 to drop the prefetch");
-  const int G = c.world;
-  fd::HostLaps L{c};
-  c.steps.fetch_add(1, std::memory_order_relaxed);
-  // Every communicator operation below is issued by this thread in one fixed order on every rank:
-  //   [counts of this batch, when not prefetched] -> {records of this batch + counts of `next`: one group}
-  //   (x_fwd, fwd comm) -> results of this batch (engine stream, back comm)
-  // 1. this batch's split sizes: exchanged by the previous call (prefetch) or now
-  int s;
-  if (use_pending) {
-    s = c.pending_slot;
-  } else {
-    s = c.next_slot;
-    c.next_slot ^= 1;
-    fd::comm_launch_counts(e, *txns, n, static_cast<hipEvent_t>(input_ready), s, L);
-  }
-  c.pending = false;
-  fd::comm_wait_counts(e, s, n, L);  // the step's one host wait (a prefetched batch's counts landed a step ago)
-  const int64_t* send = c.split[s];
-  const int64_t* recv = c.split[s] + G;
-  if (split_sizes)
-    for (int p = 0; p < 2 * G; ++p) split_sizes[p] = c.split[s][p];
-  int64_t m = 0;
-  for (int p = 0; p < G; ++p) m += recv[p];
-  // 2. this batch's records to their owners and the next batch's counts, one group on the forward stream (after the
-  // owner's previous use of the inbox slot): the counts land while this batch is scored, and the next call's wait
-  // is satisfied
-  int ns = -1;
-  if (next) {
-    ns = c.next_slot;
-    c.next_slot ^= 1;
-    c.pending = true;
-    c.pending_id = next_id;
-    c.pending_n = next_n;
-    c.pending_slot = ns;
-  }
-  fd::comm_forward_group(e, s, next, next_n, static_cast<hipEvent_t>(next_ready), ns, L);
-  // 3. the owner's features + scoring on the pipeline (features wait for the records), results on the engine stream
-  const int q = c.inbox_of[s];
-  if (m)
-    pipe_step(e, params, slots, nullptr, present, nullptr, c.inbox[q].ptr, m, nullptr, nullptr, nullptr, nullptr,
-              nullptr, nullptr, c.res[q].ptr, c.in_ev[q], /*results_in_place=*/true);
-  L(5);
-  // 4. results back (reversed splits) and into arrival order, on the engine stream
-  c.back_buf.ensure_headroom((size_t)std::max<int64_t>(n, 1) * sizeof(fd::ResultRecord));
-  fd::comm_exchange(e, true, e.stream, c.res[q].ptr, recv, c.back_buf.ptr, send, sizeof(fd::ResultRecord));
-  FD_HIP(hipEventRecord(c.inbox_ev[q], e.stream));  // the engine stream has passed this batch's results: inbox q
-  c.inbox_live[q] = true;                           // and res[q] are free for batch i + 3
-  L(6);
-  if (n) fd::launch_result_scatter(e, c.back_buf.ptr, n, d_fraud_prob, d_confidence, d_decision, d_risk);
-  L(7);
+  const fd::ShardBatch cur{txns, n, batch_id, static_cast<hipEvent_t>(input_ready)};
+  const fd::ShardBatch nxt{next, next_n, next_id, static_cast<hipEvent_t>(next_ready)};
+  fd::sharded_step(e, ms, cur, next ? &nxt : nullptr, ScoreOut{nullptr, d_fraud_prob, d_confidence, d_decision, d_risk},
+                   split_sizes);
   FD_API_END
 }
 
@@ -2177,11 +1591,8 @@ int fd_windows_step_device(fd_engine* eng, const fd_txn_batch* txns, const fd_wi
   const fd_txn_batch none_t{};
   const fd_window_inputs none_in{};
   FD_REQUIRE(txns || n == 0, FD_ERR_INVALID_ARG, "null txns");
-  Engine::Timed* tm = e.timing ? e.next_event_pair(FD_TIMING_WINDOWS) : nullptr;
-  if (tm) FD_HIP(hipEventRecord(tm->a, e.stream));
   fd::windows_step(e, txns ? *txns : none_t, in ? *in : none_in, n, flush != 0, user_out, user_cap, n_user,
-                   merchant_out, merchant_cap, n_merchant);
-  if (tm) FD_HIP(hipEventRecord(tm->b, e.stream));
+                   merchant_out, merchant_cap, n_merchant, /*timed=*/true);
   FD_API_END
 }
 
@@ -2425,7 +1836,7 @@ int fd_load_lstm(fd_engine* eng, const fd_lstm_params* params) {
   Engine& e = E(eng);
   FD_REQUIRE(params, FD_ERR_INVALID_ARG, "null params");
   FD_HIP(hipStreamSynchronize(e.stream));
-  if (e.aux_stream) FD_HIP(hipStreamSynchronize(e.aux_stream));
+  if (e.side.st[0]) FD_HIP(hipStreamSynchronize(e.side.st[0]));
   fd::load_lstm(e, *params);
   FD_API_END
 }
@@ -2435,7 +1846,7 @@ int fd_unload_lstm(fd_engine* eng) {
   FD_ENGINE_LOCK(eng);
   Engine& e = E(eng);
   FD_HIP(hipStreamSynchronize(e.stream));
-  if (e.aux_stream) FD_HIP(hipStreamSynchronize(e.aux_stream));
+  if (e.side.st[0]) FD_HIP(hipStreamSynchronize(e.side.st[0]));
   for (auto* b : {&e.lstm.wpk, &e.lstm.wpk4, &e.lstm.bias, &e.lstm.wout, &e.lstm.bout}) b->release();
   e.lstm.loaded = false;
   FD_API_END
@@ -2482,7 +1893,7 @@ int fd_pack_mlp_host(const fd_mlp_params* params, void* blob, int64_t cap, int64
 // every stream a scoring call may have put the MLP's launches on
 static void mlp_quiesce(Engine& e) {
   FD_HIP(hipStreamSynchronize(e.stream));
-  for (hipStream_t st : e.pipe_stream)
+  for (hipStream_t st : e.pipe.stream)
     if (st) FD_HIP(hipStreamSynchronize(st));
 }
 
@@ -2748,8 +2159,8 @@ int fd_ab_score_matrix_device(fd_engine* eng, int32_t test_id, const fd_ab_model
   FD_ENGINE_LOCK(eng);
   Engine& e = E(eng);
   FD_REQUIRE(control && treatment, FD_ERR_INVALID_ARG, "null model set");
-  ab_score_matrix(e, test_id, *control, *treatment, d_X, d_keys, n, ld, d_variant, d_model_probs, d_fraud_prob,
-                  d_confidence, d_decision, d_risk);
+  fd::ab_score_matrix(e, test_id, *control, *treatment, d_X, d_keys, n, ld, d_variant,
+                      ScoreOut{d_model_probs, d_fraud_prob, d_confidence, d_decision, d_risk});
   FD_API_END
 }
 
@@ -2776,27 +2187,27 @@ int fd_ab_score_matrix_host(fd_engine* eng, int32_t test_id, const fd_ab_model_s
   for (int v = 0; v < 2; ++v) {  // the external columns, n-long in arrival order
     const fd_ab_model_set& s = dset[v];
     FD_REQUIRE(s.params && s.slots, FD_ERR_INVALID_ARG, "null blend params / slots");
+    fd::require_model_count(*s.params, "n_models out of range");
     const int M = s.params->n_models;
-    FD_REQUIRE(M > 0 && M <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, "n_models out of range");
     m_max = std::max(m_max, M);
     for (int m = 0; m < M; ++m) {
-      if (s.slots[m] >= 0 || (s.present && !s.present[m])) continue;
+      if (!ModelSet(s).external(m)) continue;
       FD_REQUIRE(s.ext_probs && s.ext_probs[m], FD_ERR_INVALID_ARG,
                  "model without slot needs an external probability column");
       st.in(dext[v][m], s.ext_probs[m], (size_t)n);
     }
     dset[v].ext_probs = dext[v];
   }
-  uint8_t *dvar, *ddec, *drisk;
-  double *dMP, *dfp, *dconf;
+  uint8_t* dvar;
+  ScoreOut out;
   st.out(dvar, variant, (size_t)n);
-  st.out(dMP, model_probs, (size_t)n * m_max);
-  st.out(dfp, fraud_prob, (size_t)n);
-  st.out(dconf, confidence, (size_t)n);
-  st.out(ddec, decision, (size_t)n);
-  st.out(drisk, risk, (size_t)n);
+  st.out(out.mp, model_probs, (size_t)n * m_max);
+  st.out(out.fp, fraud_prob, (size_t)n);
+  st.out(out.conf, confidence, (size_t)n);
+  st.out(out.dec, decision, (size_t)n);
+  st.out(out.risk, risk, (size_t)n);
   st.upload();
-  ab_score_matrix(e, test_id, dset[0], dset[1], dX, dk, n, ld, dvar, dMP, dfp, dconf, ddec, drisk);
+  fd::ab_score_matrix(e, test_id, dset[0], dset[1], dX, dk, n, ld, dvar, out);
   st.download();
   FD_API_END
 }
@@ -3093,22 +2504,10 @@ int fd_score_records_device(fd_engine* eng, const fd_blend_params* params, const
   FD_ENGINE_LOCK(eng);
   Engine& e = E(eng);
   FD_REQUIRE(params && slots && n >= 0, FD_ERR_INVALID_ARG, "bad arguments");
-  for (int m = 0; m < params->n_models && m < FD_MAX_MODELS; ++m)
-    FD_REQUIRE(slots[m] >= 0 || (present && !present[m]), FD_ERR_INVALID_ARG,
-               "routed scoring needs every present model in a forest slot, FD_SLOT_LSTM or FD_SLOT_MLP");
+  const ModelSet ms(params, slots, nullptr, present);
+  fd::require_all_in_slots(ms);
   if (n == 0) return FD_OK;
-  e.feat_vec.ensure((size_t)n * FD_VECTOR_WIDTH * 4);
-  e.route_out.ensure((size_t)n * (2 * sizeof(double) + 2));
-  double* fp = e.route_out.as<double>();
-  double* conf = fp + n;
-  uint8_t* dec = reinterpret_cast<uint8_t*>(conf + n);
-  uint8_t* risk = dec + n;
-  float* sq = lstm_seq_buffer(e, *params, slots, present, n);
-  fd::launch_features_records(e, d_records, n, e.feat_vec.as<float>(), sq);  // reads the records in place
-  const auto* rec = static_cast<const fd::RouteRecord*>(d_records);
-  if (!score_matrix(e, *params, slots, nullptr, present, e.feat_vec.as<float>(), n, FD_VECTOR_WIDTH, nullptr, fp,
-                    conf, dec, risk, sq, e.state.S, rec, static_cast<fd::ResultRecord*>(d_results)))
-    fd::launch_result_pack(e, fp, conf, dec, risk, rec, n, d_results);
+  fd::score_records(e, ms, d_records, n, d_results);
   FD_API_END
 }
 
@@ -3117,7 +2516,7 @@ int fd_route_scatter_results_device(fd_engine* eng, const void* d_results, int64
   FD_API_BEGIN
   FD_ENGINE_LOCK(eng);
   Engine& e = E(eng);
-  fd::launch_result_scatter(e, d_results, n, d_fraud_prob, d_confidence, d_decision, d_risk);
+  fd::launch_result_scatter(e, d_results, n, ScoreOut{nullptr, d_fraud_prob, d_confidence, d_decision, d_risk});
   FD_API_END
 }
 
@@ -3128,7 +2527,8 @@ int fd_blend_device(fd_engine* eng, const fd_blend_params* params, int64_t n, co
   FD_ENGINE_LOCK(eng);
   Engine& e = E(eng);
   FD_REQUIRE(params, FD_ERR_INVALID_ARG, "null params");
-  fd::launch_blend(e, *params, n, d_probs, present, d_fraud_prob, d_confidence, d_decision, d_risk);
+  fd::launch_blend(e, ModelSet(params, nullptr, nullptr, present), n, d_probs,
+                   ScoreOut{nullptr, d_fraud_prob, d_confidence, d_decision, d_risk});
   FD_API_END
 }
 
@@ -3144,20 +2544,20 @@ int fd_blend_host(fd_engine* eng, const fd_blend_params* params, int64_t n, cons
   if (n == 0) return FD_OK;
   const int M = params->n_models;
   Stage st(e);
+  const ModelSet ms(params, nullptr, nullptr, present);
   const double* dcols[FD_MAX_MODELS] = {};
-  double *dfp, *dconf;
-  uint8_t *ddec, *drisk;
+  ScoreOut out;
   for (int m = 0; m < M; ++m) {  // (an absent model's column stays null: launch_blend skips it)
-    if (present && !present[m]) continue;
+    if (!ms.has(m)) continue;
     FD_REQUIRE(probs[m], FD_ERR_INVALID_ARG, "null probability column");
     st.in(dcols[m], probs[m], (size_t)n);
   }
-  st.out(dfp, fraud_prob, (size_t)n);
-  st.out(dconf, confidence, (size_t)n);
-  st.out(ddec, decision, (size_t)n);
-  st.out(drisk, risk, (size_t)n);
+  st.out(out.fp, fraud_prob, (size_t)n);
+  st.out(out.conf, confidence, (size_t)n);
+  st.out(out.dec, decision, (size_t)n);
+  st.out(out.risk, risk, (size_t)n);
   st.upload();
-  fd::launch_blend(e, *params, n, dcols, present, dfp, dconf, ddec, drisk);
+  fd::launch_blend(e, ms, n, dcols, out);
   st.download();
   FD_API_END
 }

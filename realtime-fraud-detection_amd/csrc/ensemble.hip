@@ -1081,14 +1081,13 @@ struct Pair {
 
 // The fused kernel applies (and its joint plan is built) when the batch is large and the present models are
 // exactly one XGBoost and one IsolationForest in engine slots.
-bool select_pair(Engine& e, const fd_blend_params& p, const int32_t* slots, const uint8_t* present, int64_t n,
-                 Pair& q) {
+bool select_pair(Engine& e, const ModelSet& ms, int64_t n, Pair& q) {
   if (!e.ensemble_on || e.forest_variant != 0 || n <= 0) return false;
   if ((n + kTile - 1) / kTile < kSplitTiles) return false;  // latency batches: the tree-split path
   int k = 0;
-  for (int m = 0; m < p.n_models; ++m) {
-    if (present && !present[m]) continue;
-    const int s = slots[m];
+  for (int m = 0; m < ms.n_models(); ++m) {
+    if (!ms.has(m)) continue;
+    const int s = ms.slots[m];
     if (s < 0 || s >= kMaxSlots || !e.forests[s].loaded || e.forests[s].sparse_only) return false;
     const int kind = e.forests[s].kind;
     if (kind == FD_FOREST_XGB_BINARY_LOGISTIC && q.sa < 0) {
@@ -1169,19 +1168,18 @@ bool run_plan(Engine& e, const EnsemblePlan& P, EnsArgs& a, int out, int timing_
 }
 }  // namespace
 
-bool ensemble_applies(Engine& e, const fd_blend_params& p, const int32_t* slots, const uint8_t* present, int64_t n) {
+bool ensemble_applies(Engine& e, const ModelSet& ms, int64_t n) {
   Pair q;
-  return select_pair(e, p, slots, present, n, q);
+  return select_pair(e, ms, n, q);
 }
 
-bool launch_ensemble(Engine& e, const fd_blend_params& p, const int32_t* slots, const uint8_t* present,
-                     const float* dX, int64_t n, int32_t ld, double* dMP, double* dfp, double* dconf, uint8_t* ddec,
-                     uint8_t* drisk, const RouteRecord* records, ResultRecord* results, int compact) {
+bool launch_ensemble(Engine& e, const ModelSet& ms, const ScoreRows& rows, const ScoreOut& out_cols) {
   Pair q;
-  if (!select_pair(e, p, slots, present, n, q)) return false;
+  if (!select_pair(e, ms, rows.n, q)) return false;
   const int pa = q.pa, pb = q.pb, ma = q.ma, mb = q.mb;
+  const int compact = rows.compact;
   EnsArgs a{};
-  plan_args(e.ens, dX, n, compact ? kCompactWidth : ld, e.ens_owner_fixed, a);
+  plan_args(e.ens, rows.X, rows.n, compact ? kCompactWidth : rows.ld, e.ens_owner_fixed, a);
   a.compact = compact;
   if (compact && e.ens_bin_global) {  // one pass, every table searched where it lies (L2), nothing staged
     a.n_pass = 1;
@@ -1194,16 +1192,16 @@ bool launch_ensemble(Engine& e, const fd_blend_params& p, const int32_t* slots, 
   a.pos[1] = pb;
   a.mcol[0] = ma;
   a.mcol[1] = mb;
-  a.blend = blend_consts(p, present);
-  a.mp = dMP;
-  a.fp = dfp;
-  a.conf = dconf;
-  a.dec = ddec;
-  a.risk = drisk;
-  a.rec = records;
-  a.res = results;
-  const int out = results ? 1 : 0;
-  FD_REQUIRE(out == 1 || dfp != nullptr, FD_ERR_INVALID_ARG, "null output");
+  a.blend = blend_consts(ms);
+  a.mp = out_cols.mp;
+  a.fp = out_cols.fp;
+  a.conf = out_cols.conf;
+  a.dec = out_cols.dec;
+  a.risk = out_cols.risk;
+  a.rec = rows.records;
+  a.res = rows.results;
+  const int out = rows.results ? 1 : 0;
+  FD_REQUIRE(out == 1 || out_cols.fp != nullptr, FD_ERR_INVALID_ARG, "null output");
   // compact / split rows carry the constant slots' values by construction: the contracted chunks and the
   // variable-depth walk, when the contraction shortened any tree; 64-wide rows keep nodes[] and the fixed-depth kernels
   // (the kernel's VD: 1 per tree, 2 per wave, 3 the dense chunk stream of ensemble_contract 3 / 4)

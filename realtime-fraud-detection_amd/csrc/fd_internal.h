@@ -399,7 +399,7 @@ struct AbState {
   DeviceBuffer state;     // fd_ab_state per test id
   DeviceBuffer partials;  // one fd_ab_state per workgroup of the record kernel, then its ticket
   DeviceBuffer part;      // partition: control rows per workgroup, scanned in place
-  DeviceBuffer index;     // fd_ab_score_matrix_* (engine.hip): the partition's index, its two counts, the variants
+  DeviceBuffer index;     // fd_ab_score_matrix_* (score.hip ab_score_matrix): the partition's index, its two counts, the variants
   DeviceBuffer rows;      // ... and the batch in partition order with its results
 };
 // Prediction metrics (metrics.hip): the collector's state on the device, the ring's header on the host
@@ -614,7 +614,7 @@ struct IngestTables {
   int stop_after = 0;  // diagnostics option "ingest_stop_after"
 };
 
-// the engine's own RCCL communicators and buffers for the sharded step (comm.hip, fd_sharded_step in engine.hip);
+// the engine's own RCCL communicators and buffers for the sharded step (comm.hip, sharded_step there);
 // per-batch buffers in two slots (a step's batch and the next one, prefetched)
 struct ShardComm {
   bool ready = false;
@@ -696,6 +696,151 @@ inline int64_t floor_div_host(int64_t a, int64_t b) {
   return q;
 }
 
+// ---- the arguments of the scoring schedulers (score.hip), named. Host side only: passed by const&, never a
+// kernel's parameter (the launch sites hand the kernels the members).
+
+// The models of one scoring call: blend parameters, slots[m] (a forest slot, FD_SLOT_LSTM, FD_SLOT_MLP, or < 0 for an
+// external probability column ext[m]) and present[m] (null: all present). The public fd_ab_model_set's four members.
+struct ModelSet {
+  const fd_blend_params* params = nullptr;
+  const int32_t* slots = nullptr;
+  const double* const* ext = nullptr;
+  const uint8_t* present = nullptr;
+  ModelSet(const fd_blend_params* p, const int32_t* s, const double* const* x, const uint8_t* pr)
+      : params(p), slots(s), ext(x), present(pr) {}
+  explicit ModelSet(const fd_ab_model_set& s) : ModelSet(s.params, s.slots, s.ext_probs, s.present) {}
+  int n_models() const { return params->n_models; }
+  bool has(int m) const { return !(present && !present[m]); }
+  // model m sits in a forest slot (present or not; the slot may still be out of range: slot_of checks)
+  bool forest(int m) const { return slots[m] >= 0 && slots[m] != FD_SLOT_LSTM && slots[m] != FD_SLOT_MLP; }
+  bool external(int m) const { return slots[m] < 0 && has(m); }  // present and scored by the caller: ext[m]
+  bool wants_lstm() const {  // a present model is the LSTM head: the batch needs card-history sequences
+    for (int m = 0; m < n_models() && m < FD_MAX_MODELS; ++m)
+      if (slots && slots[m] == FD_SLOT_LSTM && has(m)) return true;
+    return false;
+  }
+  bool all_in_slots() const {  // no present model is external (routed scoring has no place for a column)
+    for (int m = 0; m < n_models() && m < FD_MAX_MODELS; ++m)
+      if (external(m)) return false;
+    return true;
+  }
+};
+// one text per entry point ("n_models out of range" / "bad n_models"): the helper takes it
+inline void require_model_count(const fd_blend_params& p, const char* text) {
+  FD_REQUIRE(p.n_models > 0 && p.n_models <= FD_MAX_MODELS, FD_ERR_INVALID_ARG, text);
+}
+inline void require_all_in_slots(const ModelSet& ms) {
+  FD_REQUIRE(ms.all_in_slots(), FD_ERR_INVALID_ARG,
+             "routed scoring needs every present model in a forest slot, FD_SLOT_LSTM or FD_SLOT_MLP");
+}
+
+// The outputs of one scoring call: the per-model matrix (n_models x n, column-major; optional) and the four blended
+// columns (fp required where columns are written at all; the others optional)
+struct ScoreOut {
+  double* mp = nullptr;
+  double* fp = nullptr;
+  double* conf = nullptr;
+  uint8_t* dec = nullptr;
+  uint8_t* risk = nullptr;
+  // the same columns from row `first` on, nulls staying null; the matrix of those rows is the caller's to name
+  ScoreOut rows_from(int64_t first, double* mp_rows = nullptr) const {
+    return {mp_rows, fp ? fp + first : nullptr, conf ? conf + first : nullptr, dec ? dec + first : nullptr,
+            risk ? risk + first : nullptr};
+  }
+};
+
+// The rows score_matrix scores: the matrix, and what only some callers have — the LSTM head's sequences (n x T x 16,
+// with the latency path's descriptors), the routed records with the result records to write, compact / split rows
+struct ScoreRows {
+  const float* X;
+  int64_t n;
+  int32_t ld;
+  ScoreRows(const float* X_, int64_t n_, int32_t ld_) : X(X_), n(n_), ld(ld_) {}
+  const float* seq = nullptr;
+  int T = 0;
+  const unsigned long long* seq_desc = nullptr;
+  const RouteRecord* records = nullptr;
+  ResultRecord* results = nullptr;
+  int compact = 0;  // 1 / 2: X holds compact / split rows (launch_ensemble), the fused kernel only
+};
+
+// One micro-batch of the pipelined stream (pipe_step): transaction columns (txns) whose scores go to `out` (and the
+// vectors to d_vectors), or routed 48-B records whose scores leave as 24-B result records in d_results
+struct PipeBatch {
+  const fd_txn_batch* txns = nullptr;
+  const void* records = nullptr;
+  int64_t n = 0;
+  float* d_vectors = nullptr;
+  ScoreOut out;
+  void* d_results = nullptr;
+  void* input_ready = nullptr;    // hipEvent_t: the inputs are complete
+  bool results_in_place = false;  // d_results is the engine's own buffer: no staging copy (fd_sharded_step)
+};
+
+// score_matrix's side streams: [0] the LSTM head (and, small_streams 1, every forest after the first), [1] small
+// batches under small_streams 2: the forests after the first. Created on first use.
+struct SideStreams {
+  hipStream_t st[2] = {};
+  hipEvent_t fork_ev = nullptr, join_ev[2] = {};
+  void fork(int k, hipStream_t from);  // st[k] after everything queued on `from` so far
+  hipEvent_t mark(int k);              // an event recorded on st[k] now
+  void join(int k, hipStream_t to);    // `to` after everything queued on st[k] so far
+  void release();
+};
+
+// The pipelined stream (fd_score_batch_pipelined / fd_score_records_pipelined / fd_sharded_step; score.hip pipe_step):
+// features and scoring of batch i on stream[i & 1] (no cross-stream wait between a batch's features and its forests;
+// batch i-1's features waited for by event); vectors / LSTM sequences double-buffered by batch parity
+struct Pipeline {
+  static constexpr int kSlots = 2;
+  hipStream_t stream[2] = {nullptr, nullptr};
+  // batch i's scoring-done event is done_ev[i mod kDoneRing]: the engine stream, the next batch of a per-model
+  // scoring path and — split rows — batch i + 4's slot pass (which rewrites the ring buffer batch i's fused kernel
+  // read) wait on it
+  static constexpr int kDoneRing = 4;
+  hipEvent_t entry_ev = nullptr, feat_ev[kSlots] = {}, done_ev[kDoneRing] = {};
+  bool feat_live[kSlots] = {}, done_live[kDoneRing] = {};
+  bool dirty = true;  // another engine call since the last pipelined one: order after the engine stream first
+  // option "slot_stream" (0 off, 1 high-priority stream, 2 low): batch i's slot pass on a stream of its own, so it
+  // does not queue behind batch i-2's fused kernel on stream[i & 1]; its bucket pass waits for it by event.
+  // -1 (default) auto: 2 when the card table has >= 2^26 slots, else 0. Config 4 (2^27 slots): 0.0915 -> 0.0897 ms
+  // per step at 2 (1: 0.0906); config 3 (10 M cards): 0.0876 -> 0.0948 (DESIGN §3)
+  int slot_mode = -1;
+  hipStream_t slot_stream = nullptr;
+  hipEvent_t slot_ev[kSlots] = {};
+  // launch_grouped's slot pass goes to this stream (then an event the bucket pass's stream waits for) while set
+  hipStream_t slot_pass_stream = nullptr;
+  hipEvent_t slot_pass_ev = nullptr;
+  unsigned long long iter = 0;
+  unsigned long long iter_total = 0;         // counter "pipelined_batches"
+  unsigned long long compact_total = 0;      // counter "pipelined_compact_batches": batches scored from compact vectors
+  unsigned long long split_total = 0;        // counter "pipelined_split_batches": of those, split rows
+  unsigned long long host_ns = 0;            // counter "pipelined_host_ns": host time inside fd_score_batch_pipelined
+  unsigned long long slot_stream_total = 0;  // counter "pipelined_slot_stream_batches": slot pass on its own stream
+  bool lean = true;    // "pipeline_lean" option: lean bucket kernel (fits beside the ensemble kernel)
+  bool gather = true;  // "pipeline_gather" option: batches of <= kGatherBatchMax take the gather bucket kernel
+  DeviceBuffer vec[kSlots], seq[kSlots];
+  // split rows (compact_vectors 2): RowA | RowB of batch i in ring buffer i mod kSplitRing. With the slot pass on its
+  // own stream, batch i's slot kernel writes RowA while batch i - 2's fused kernel (the same vec parity) may still
+  // read its rows — the slot stream waits only for batch i - 2's bucket pass — so the split rows get a deeper ring,
+  // and the slot pass waits for the fused kernel that last read its buffer (batch i - 4's done_ev: long done)
+  static constexpr int kSplitRing = 4;
+  static_assert(kSplitRing == kDoneRing, "the split-row ring's buffers are released by the done events");
+  DeviceBuffer split[kSplitRing];
+  // the scoring streams write a batch's outputs into out[slot]; one copy kernel on the engine stream moves them to
+  // the caller's buffers, so the caller's memory is written only in the engine stream's order (torch's caching
+  // allocator may hand batch i's freed outputs to batch i+1); batch i+2's scoring waits for copy_ev[slot]
+  DeviceBuffer out[kSlots];
+  hipEvent_t copy_ev[kSlots] = {};
+  bool copy_live[kSlots] = {};
+  bool copy_vec[kSlots] = {};  // that copy also read the slot's vectors (the slot's next features wait)
+  // first use: the streams (option stream_priority) and events; slot_mode -1 resolved by the card table's size
+  void create(int stream_prio, bool big_table);
+  void release();  // streams drained and destroyed, events destroyed, buffers freed
+  // stream s after the scoring of every pipelined batch so far (a new engine stream inherits the old one's order)
+  void order_after_scoring(hipStream_t s);
+};
+
 struct Engine {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -712,37 +857,11 @@ struct Engine {
   WindowState windows;
   IngestTables ingest;
   SinkState sink;
-  hipStream_t aux_stream = nullptr;            // LSTM head runs here, concurrent with the forests
-  hipEvent_t fork_ev = nullptr, join_ev = nullptr;
-  hipStream_t aux2_stream = nullptr;           // small batches: the second forest, concurrent with the first
-  hipEvent_t join2_ev = nullptr;
+  SideStreams side;                            // score_matrix's side streams (score.hip)
   DeviceBuffer seq_buf;                        // per-txn LSTM input sequences of the fused path
   DeviceBuffer seq_desc;                       // latency path: per-txn sequence descriptors (kSeqMaterialized)
   DeviceBuffer feat_vec, feat_ext;  // feature vectors of the scoring entry points / extended-feature scratch
-  // fd_score_batch_pipelined (engine.hip): features and scoring of batch i on pipe_stream[i & 1] (no cross-stream
-  // wait between a batch's features and its forests; batch i-1's features waited for by event); vectors / LSTM
-  // sequences double-buffered by batch parity
-  static constexpr int kPipeSlots = 2;
-  hipStream_t pipe_stream[2] = {nullptr, nullptr};
-  // batch i's scoring-done event is pipe_done_ev[i mod kDoneRing]: the engine stream, the next batch of a per-model
-  // scoring path and — split rows — batch i + 4's slot pass (which rewrites the ring buffer batch i's fused kernel
-  // read) wait on it
-  static constexpr int kDoneRing = 4;
-  hipEvent_t pipe_entry_ev = nullptr, pipe_feat_ev[kPipeSlots] = {}, pipe_done_ev[kDoneRing] = {};
-  bool pipe_feat_live[kPipeSlots] = {}, pipe_done_live[kDoneRing] = {};
-  bool pipe_dirty = true;  // another engine call since the last pipelined one: order after `stream` first
-  // option "slot_stream" (0 off, 1 high-priority stream, 2 low): batch i's slot pass on a stream of its own, so it
-  // does not queue behind batch i-2's fused kernel on pipe_stream[i & 1]; its bucket pass waits for it by event.
-  // -1 (default) auto: 2 when the card table has >= 2^26 slots, else 0. Config 4 (2^27 slots): 0.0915 -> 0.0897 ms
-  // per step at 2 (1: 0.0906); config 3 (10 M cards): 0.0876 -> 0.0948 (DESIGN §3)
-  int pipe_slot_mode = -1;
-  hipStream_t pipe_slot_stream = nullptr;
-  hipEvent_t pipe_slot_ev[kPipeSlots] = {};
-  // launch_grouped's slot pass goes to this stream (then an event the bucket pass's stream waits for) while set
-  hipStream_t slot_pass_stream = nullptr;
-  hipEvent_t slot_pass_ev = nullptr;
-  unsigned long long pipe_iter = 0;
-  unsigned long long pipe_iter_total = 0;  // counter "pipelined_batches"
+  Pipeline pipe;                               // the pipelined stream (score.hip pipe_step)
   unsigned long long sparse_total = 0;        // counter "forest_sparse_launches": launches of forest_sparse_kernel
   unsigned long long shap_total = 0;          // counter "forest_shap_launches": launches of shap_kernel
   DeviceBuffer shap_partial;                  // shap.hip: per-chunk sums of one row batch, [chunk][column][row]
@@ -750,29 +869,7 @@ struct Engine {
   IForestFitScratch iforest;                  // iforest_fit.hip: the fit's device buffers and counters
   unsigned long long ens_single_total = 0;    // counter "ensemble_single_launches": fd_forest_predict batches run by
                                               // the fused kernel over one forest (config 2's timed kernel)
-  unsigned long long pipe_split_total = 0;    // counter "pipelined_split_batches": of those, split rows
-  unsigned long long pipe_compact_total = 0;  // counter "pipelined_compact_batches": batches scored from compact vectors
-  unsigned long long pipe_host_ns = 0;  // counter "pipelined_host_ns": host time inside fd_score_batch_pipelined
-  unsigned long long pipe_slot_stream_total = 0;  // counter "pipelined_slot_stream_batches": slot pass on its own stream
-  bool pipe_lean = true;   // "pipeline_lean" option: lean bucket kernel (fits beside the ensemble kernel)
-  bool pipe_gather = true;  // "pipeline_gather" option: batches of <= kGatherBatchMax take the gather bucket kernel
-  DeviceBuffer pipe_vec[kPipeSlots], pipe_seq[kPipeSlots];
-  // split rows (compact_vectors 2): RowA | RowB of batch i in ring buffer i mod kSplitRing. With the slot pass on its
-  // own stream, batch i's slot kernel writes RowA while batch i - 2's fused kernel (the same pipe_vec parity) may
-  // still read its rows — the slot stream waits only for batch i - 2's bucket pass — so the split rows get a deeper
-  // ring, and the slot pass waits for the fused kernel that last read its buffer (batch i - 4's pipe_done_ev: long
-  // done)
-  static constexpr int kSplitRing = 4;
-  static_assert(kSplitRing == kDoneRing, "the split-row ring's buffers are released by the done events");
-  DeviceBuffer pipe_split[kSplitRing];
-  // the scoring streams write a batch's outputs into pipe_out[slot]; one copy kernel on `stream` moves them to the
-  // caller's buffers, so the caller's memory is written only in the engine stream's order (torch's caching
-  // allocator may hand batch i's freed outputs to batch i+1); batch i+nbuf's scoring waits for pipe_copy_ev[slot]
-  DeviceBuffer pipe_out[kPipeSlots];
-  hipEvent_t pipe_copy_ev[kPipeSlots] = {};
-  bool pipe_copy_live[kPipeSlots] = {};
-  bool pipe_copy_vec[kPipeSlots] = {};  // that copy also read the slot's vectors (the slot's next features wait)
-  int small_streams = 0;  // score_matrix, latency batches: side streams for the LSTM / other forests (engine.hip)
+  int small_streams = 0;  // score_matrix, latency batches: side streams for the LSTM / other forests (score.hip)
   bool latency_fused = true;  // "latency_fused": latency pair walk + sums + blend in 2 launches (forest.hip)
   bool seq_ring_lstm = true;  // "seq_ring_lstm": latency batches' LSTM reads card histories from the ring
   bool latency_prebin = true;  // "latency_prebin": the latency pair's binning in the LSTM head's launch (PreBin)
@@ -782,12 +879,12 @@ struct Engine {
   PreBin prebin;
   unsigned long long prebin_total = 0;  // counter "latency_prebinned_batches"
   bool ens_prio = true;   // "ensemble_prio": the fused kernel's waves issue at priority 2 (above the feature kernels;
-                          // the default since round 6's split rows, engine.hip)
+                          // the default since round 6's split rows, score.hip pipe_step)
   bool ens_bin_global = false;  // "ensemble_bin_global": compact rows binned by searches in global memory (no staging)
   int compact_vectors = 2;      // "compact_vectors": the pipelined stream's scoring rows for the fused kernel when
                                 // nobody asked for vectors: 0 the 64-wide vector, 1 compact 64-B rows, 2 split rows
-                                // (card-independent half from the slot pass; engine.hip, features.hip Prep32)
-  int stream_prio = 3;    // option "stream_priority": the pipeline / forward streams' HIP priorities (engine.hip)
+                                // (card-independent half from the slot pass; score.hip pipe_step, features.hip Prep32)
+  int stream_prio = 3;    // option "stream_priority": the pipeline / forward streams' HIP priorities (score.hip Pipeline::create, comm.hip)
   DeviceBuffer stage;          // the host (`_host`) entry points' staged inputs and outputs (engine.hip Stage)
   DeviceBuffer scratch_probs;  // score_matrix per-model columns
   DeviceBuffer route_blk, route_out, route_err;  // card-hash routing scratch (route.hip)
@@ -881,8 +978,7 @@ void launch_forest(Engine& e, const PackedForest& pf, const float* d_X, int64_t 
 struct BlendConsts;
 bool launch_forest_pair_blend(Engine& e, const PackedForest& p1, const PackedForest& p2, const float* d_X, int64_t n,
                               int32_t ld, const BlendConsts& bc, const double* const* cols, int pos1, int pos2,
-                              double* dfp, double* dconf, uint8_t* ddec, uint8_t* drisk,
-                              hipEvent_t before_blend = nullptr);
+                              const ScoreOut& out, hipEvent_t before_blend = nullptr);
 // e.prebin for the pair launch_forest_pair_blend will run over d_X (n rows): false (e.prebin.want cleared) when it
 // does not apply
 bool forest_pair_prebin(Engine& e, const PackedForest& p1, const PackedForest& p2, const float* d_X, int64_t n,
@@ -891,7 +987,7 @@ bool forest_pair_prebin(Engine& e, const PackedForest& p1, const PackedForest& p
 void windows_init(Engine& e, const fd_window_params& p);
 void windows_step(Engine& e, const fd_txn_batch& t, const fd_window_inputs& in, int64_t n, bool flush,
                   fd_user_window* u_out, int64_t u_cap, int64_t* n_user, fd_merchant_window* m_out, int64_t m_cap,
-                  int64_t* n_merch);
+                  int64_t* n_merch, bool timed = false);  // timed: an FD_TIMING_WINDOWS event pair around the step
 void windows_release(Engine& e);
 void windows_observe(Engine& e, int64_t max_event_ts);
 void merchant_windows_merge(const fd_merchant_window* p, int64_t n, fd_merchant_window* out, int64_t* n_out);
@@ -930,8 +1026,24 @@ void load_vocab(Engine& e, const uint8_t* pay_high_risk, const uint8_t* type_ref
 void launch_features_full(Engine& e, const fd_txn_batch& t, const fd_txn_context& c, int64_t n, float* d_vec,
                           double* d_raw, double* d_fmap, fd_rule_scores* d_rules);
 void features_check(Engine& e);
-// engine.hip: a non-blocking stream at HIP priority level (+1 the greatest, -1 the least, 0 the default)
+// score.hip: the scoring schedulers behind fd_score_matrix_* / fd_score_batch_* / fd_score_records_* /
+// fd_ab_score_matrix_* (device pointers; everything on e.stream unless said otherwise)
+// a non-blocking stream at HIP priority level (+1 the greatest, -1 the least, 0 the default)
 hipStream_t make_stream(int level);
+PackedForest& slot_of(Engine& e, int slot);  // FD_ERR_INVALID_ARG when out of range
+// every model of the set over the rows, then the blend. true: the route result records (rows.results) were written
+// too (the fused ensemble kernel's epilogue); otherwise the caller packs them from the columns
+bool score_matrix(Engine& e, const ModelSet& ms, const ScoreRows& rows, const ScoreOut& out);
+// features (card state updated) -> score_matrix; d_vectors null: the vectors stay in engine scratch
+void score_batch(Engine& e, const ModelSet& ms, const fd_txn_batch& t, int64_t n, float* d_vectors,
+                 const ScoreOut& out);
+// the same over routed 48-B records, the scores leaving as 24-B result records
+void score_records(Engine& e, const ModelSet& ms, const void* d_records, int64_t n, void* d_results);
+// score_matrix with one model set per A/B variant, results in arrival order (waits once, for the partition's counts)
+void ab_score_matrix(Engine& e, int id, const fd_ab_model_set& c, const fd_ab_model_set& t, const float* dX,
+                     const uint64_t* d_keys, int64_t n, int32_t ld, uint8_t* d_variant, const ScoreOut& out);
+// one micro-batch of the pipelined stream: features and scoring on the pipeline's streams, outputs on e.stream
+void pipe_step(Engine& e, const ModelSet& ms, const PipeBatch& b);
 // route.hip
 unsigned shard_of_host(unsigned long long key, unsigned G);
 // stream / scratch: the launch stream and block-count scratch (default: the engine stream and route_blk)
@@ -955,10 +1067,9 @@ void launch_route_place(const fd_txn_batch& t, int64_t n, int G, void* d_records
                         const CountPublish* pub = nullptr);
 void launch_route_unpack(Engine& e, const void* d_records, const void* d_results, int64_t n, const fd_txn_batch& out,
                          uint8_t* pm, uint8_t* fraud, double* score);
-void launch_result_pack(Engine& e, const double* fp, const double* conf, const uint8_t* dec, const uint8_t* risk,
-                        const RouteRecord* records, int64_t n, void* d_results);
-void launch_result_scatter(Engine& e, const void* d_results, int64_t n, double* fp, double* conf, uint8_t* dec,
-                           uint8_t* risk);
+// the blended columns of `cols` (its matrix unused) into result records / result records back into columns
+void launch_result_pack(Engine& e, const ScoreOut& cols, const RouteRecord* records, int64_t n, void* d_results);
+void launch_result_scatter(Engine& e, const void* d_results, int64_t n, const ScoreOut& out);
 void route_check(Engine& e);
 // comm.hip
 void comm_unique_id(const char* rccl_path, uint8_t* out);
@@ -970,9 +1081,19 @@ void comm_abort(Engine& e, const std::string& reason);
 bool comm_sync_stream(Engine& e, hipStream_t st);
 void comm_launch_counts(Engine& e, const fd_txn_batch& t, int64_t n, hipEvent_t ready, int slot, HostLaps& L);
 void comm_wait_counts(Engine& e, int slot, int64_t n, HostLaps& L);  // host wait; split[slot] checked
+// a batch as fd_sharded_step names it: its columns, its id (0: not prefetched) and the event its inputs wait for
+struct ShardBatch {
+  const fd_txn_batch* txns;
+  int64_t n;
+  uint64_t id;
+  hipEvent_t ready;
+};
 // records exchange of `slot` behind its inbox slot, + the next batch's count exchange in the same group
-void comm_forward_group(Engine& e, int slot, const fd_txn_batch* next, int64_t next_n, hipEvent_t next_ready,
-                        int next_slot, HostLaps& L);
+void comm_forward_group(Engine& e, int slot, const ShardBatch* next, int next_slot, HostLaps& L);
+// one sharded step: this batch's counts (unless prefetched: cur.id names the pending batch), records out, the
+// owner's pipe_step, results back into `out` in arrival order; `next`: the batch to prefetch the counts of
+void sharded_step(Engine& e, const ModelSet& ms, const ShardBatch& cur, const ShardBatch* next, const ScoreOut& out,
+                  int64_t* split_sizes);
 void comm_exchange(Engine& e, bool back, hipStream_t st, const void* sendbuf, const int64_t* send, void* recvbuf,
                    const int64_t* recv, size_t elem);
 // lstm.hip
@@ -1108,19 +1229,17 @@ void launch_shap_topk(Engine& e, const double* d_phi, int64_t n, int32_t ld_phi,
 // ensemble.hip: the fused path when the present models are one XGBoost and/or one IsolationForest in engine
 // slots and the batch is large (false: not applicable, the caller runs the per-model kernels + blend).
 // results != nullptr: write route result records (seq from records[i]) instead of the columns.
-bool ensemble_applies(Engine& e, const fd_blend_params& p, const int32_t* slots, const uint8_t* present, int64_t n);
+bool ensemble_applies(Engine& e, const ModelSet& ms, int64_t n);
 // one forest's probabilities through the fused kernel (large batches, no raw / leaf outputs); false: not applicable
 bool launch_ensemble_single(Engine& e, int slot, const float* dX, int64_t n, int32_t ld, double* dprob,
                             double* draw, hipStream_t stream);
-// compact: 1 dX rows are the compact vector (64-B rows of kCompactWidth words, ld ignored; the plan's features <= 64);
-// 2 split rows (RowA [n] then RowB [n] at dX, features.hip)
-bool launch_ensemble(Engine& e, const fd_blend_params& p, const int32_t* slots, const uint8_t* present,
-                     const float* dX, int64_t n, int32_t ld, double* dMP, double* dfp, double* dconf, uint8_t* ddec,
-                     uint8_t* drisk, const RouteRecord* records, ResultRecord* results, int compact = 0);
+// rows.compact: 1 the rows are the compact vector (64-B rows of kCompactWidth words, ld ignored; the plan's features
+// <= 64); 2 split rows (RowA [n] then RowB [n] at rows.X, features.hip)
+bool launch_ensemble(Engine& e, const ModelSet& ms, const ScoreRows& rows, const ScoreOut& out);
 // ensemble_plan.hip: the host copy of a loaded forest, which the joint plans are built from
 void forest_loaded(PackedForest& pf, const fd_forest_params& p, const fd_tree_arrays& t);
 // blend.hip
-void launch_blend(Engine& e, const fd_blend_params& p, int64_t n, const double* const* d_probs,
-                  const uint8_t* present, double* d_fp, double* d_conf, uint8_t* d_dec, uint8_t* d_risk);
+// d_probs[m]: model m's probability column (an absent model's may be null); ms.slots / ms.ext are not read
+void launch_blend(Engine& e, const ModelSet& ms, int64_t n, const double* const* d_probs, const ScoreOut& out);
 
 }  // namespace fd

@@ -2066,7 +2066,7 @@ void launch_grouped(Engine& e, const TxnSrc& src, int64_t n, float* d_vec, doubl
   const int par = g.batch_parity;
   g.batch_parity ^= 1;
   // the slot pass on the engine's slot stream when the pipelined step set one (option slot_stream), else on s
-  const hipStream_t ss = e.slot_pass_stream ? e.slot_pass_stream : s;
+  const hipStream_t ss = e.pipe.slot_pass_stream ? e.pipe.slot_pass_stream : s;
   // latency batches: the slot pass inside the bucket kernel (no slot launch; its probes in the card loop's launch)
   const bool gather = st.slot_gather && !lean && n <= (int64_t)kChunkCap && ss == s;  // (never with split: lean)
   Engine::Timed* ev = e.timing ? e.next_event_pair(FD_TIMING_FEATURES) : nullptr;
@@ -2079,8 +2079,8 @@ void launch_grouped(Engine& e, const TxnSrc& src, int64_t n, float* d_vec, doubl
                      st.err.as<unsigned>(), lean && st.slot_prio ? 1 : 0, row_a);
   FD_HIP(hipGetLastError());
   if (ss != s) {
-    FD_HIP(hipEventRecord(e.slot_pass_ev, ss));
-    FD_HIP(hipStreamWaitEvent(s, e.slot_pass_ev, 0));
+    FD_HIP(hipEventRecord(e.pipe.slot_pass_ev, ss));
+    FD_HIP(hipStreamWaitEvent(s, e.pipe.slot_pass_ev, 0));
   }
   if (before_buckets) FD_HIP(hipStreamWaitEvent(s, before_buckets, 0));
   if (ev && ss != s) {  // timed in two parts: the slot pass on ss, the bucket pass from here on s

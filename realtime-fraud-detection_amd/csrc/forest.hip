@@ -1127,7 +1127,7 @@ bool forest_pair_prebin(Engine& e, const PackedForest& p1, const PackedForest& p
 
 bool launch_forest_pair_blend(Engine& e, const PackedForest& p1, const PackedForest& p2, const float* d_X, int64_t n,
                               int32_t ld, const BlendConsts& bc, const double* const* cols, int pos1, int pos2,
-                              double* dfp, double* dconf, uint8_t* ddec, uint8_t* drisk, hipEvent_t before_blend) {
+                              const ScoreOut& out, hipEvent_t before_blend) {
   const PackedForest *xf = nullptr, *ff = nullptr;
   WalkPairFn walk = nullptr;
   size_t lds = 0;
@@ -1139,7 +1139,7 @@ bool launch_forest_pair_blend(Engine& e, const PackedForest& p1, const PackedFor
   if (!pair_blend_plan(e, p1, p2, n, xf, ff, walk, lds)) return false;
   const PackedForest& X = *xf;
   const PackedForest& F = *ff;
-  FD_REQUIRE(d_X && dfp && cols && ld > 0, FD_ERR_INVALID_ARG, "null buffer or bad ld");
+  FD_REQUIRE(d_X && out.fp && cols && ld > 0, FD_ERR_INVALID_ARG, "null buffer or bad ld");
   const int64_t tiles = (n + kTile - 1) / kTile, n_pad = tiles * kTile;
   const hipStream_t st = e.stream;
   Engine::Timed* ev = e.timing ? e.next_event_pair(FD_TIMING_XGB) : nullptr;  // the pair's launches
@@ -1167,10 +1167,10 @@ bool launch_forest_pair_blend(Engine& e, const PackedForest& p1, const PackedFor
   pa.base_margin = X.base_margin;
   pa.if_offset = F.if_offset;
   pa.if_denom = F.if_denominator;
-  pa.fp = dfp;
-  pa.conf = dconf;
-  pa.dec = ddec;
-  pa.risk = drisk;
+  pa.fp = out.fp;
+  pa.conf = out.conf;
+  pa.dec = out.dec;
+  pa.risk = out.risk;
   if (before_blend) FD_HIP(hipStreamWaitEvent(st, before_blend, 0));  // e.g. the LSTM head on a side stream
   hipLaunchKernelGGL(split_sum_pair_blend_kernel, dim3((unsigned)((n + kPairRows - 1) / kPairRows)), dim3(256), 0, st,
                      X.split.leaves.as<const float>(), X.n_trees, F.split.leaves.as<const double>(), F.n_trees, n, pa,

@@ -291,27 +291,26 @@ void launch_route_unpack(Engine& e, const void* d_records, const void* d_results
   FD_HIP(hipGetLastError());
 }
 
-void launch_result_pack(Engine& e, const double* fp, const double* conf, const uint8_t* dec, const uint8_t* risk,
-                        const RouteRecord* records, int64_t n, void* d_results) {
+void launch_result_pack(Engine& e, const ScoreOut& cols, const RouteRecord* records, int64_t n, void* d_results) {
   if (n == 0) return;
   FD_REQUIRE(d_results != nullptr, FD_ERR_INVALID_ARG, "null result records");
-  hipLaunchKernelGGL(result_pack_kernel, dim3(grid256(n)), dim3(256), 0, e.stream, fp, conf, dec, risk, records, n,
-                     static_cast<ResultRecord*>(d_results));
+  hipLaunchKernelGGL(result_pack_kernel, dim3(grid256(n)), dim3(256), 0, e.stream, cols.fp, cols.conf, cols.dec,
+                     cols.risk, records, n, static_cast<ResultRecord*>(d_results));
   FD_HIP(hipGetLastError());
 }
 
-void launch_result_scatter(Engine& e, const void* d_results, int64_t n, double* fp, double* conf, uint8_t* dec,
-                           uint8_t* risk) {
+void launch_result_scatter(Engine& e, const void* d_results, int64_t n, const ScoreOut& out) {
   FD_REQUIRE(n >= 0 && n < (1ll << 31), FD_ERR_INVALID_ARG, "batch size out of range");
   if (n == 0) return;
-  FD_REQUIRE(d_results && fp, FD_ERR_INVALID_ARG, "null result records / output");
+  FD_REQUIRE(d_results && out.fp, FD_ERR_INVALID_ARG, "null result records / output");
   if (!e.route_err_live) {
     e.route_err.ensure(16);
     FD_HIP(hipMemsetAsync(e.route_err.ptr, 0, 16, e.stream));
     e.route_err_live = true;
   }
   hipLaunchKernelGGL(result_scatter_kernel, dim3(grid256(n)), dim3(256), 0, e.stream,
-                     static_cast<const ResultRecord*>(d_results), n, fp, conf, dec, risk, e.route_err.as<unsigned>());
+                     static_cast<const ResultRecord*>(d_results), n, out.fp, out.conf, out.dec, out.risk,
+                     e.route_err.as<unsigned>());
   FD_HIP(hipGetLastError());
 }
 

@@ -393,9 +393,22 @@ void windows_sort(Engine& e, unsigned n, unsigned long long** k_out, unsigned** 
 
 }  // namespace
 
+static void step(Engine& e, const fd_txn_batch& t, const fd_window_inputs& in, int64_t n, bool flush,
+                 fd_user_window* u_out, int64_t u_cap, int64_t* n_user, fd_merchant_window* m_out, int64_t m_cap,
+                 int64_t* n_merch);
+
 void windows_step(Engine& e, const fd_txn_batch& t, const fd_window_inputs& in, int64_t n, bool flush,
                   fd_user_window* u_out, int64_t u_cap, int64_t* n_user, fd_merchant_window* m_out, int64_t m_cap,
-                  int64_t* n_merch) {
+                  int64_t* n_merch, bool timed) {
+  Engine::Timed* tm = timed && e.timing ? e.next_event_pair(FD_TIMING_WINDOWS) : nullptr;
+  if (tm) FD_HIP(hipEventRecord(tm->a, e.stream));
+  step(e, t, in, n, flush, u_out, u_cap, n_user, m_out, m_cap, n_merch);
+  if (tm) FD_HIP(hipEventRecord(tm->b, e.stream));
+}
+
+static void step(Engine& e, const fd_txn_batch& t, const fd_window_inputs& in, int64_t n, bool flush,
+                 fd_user_window* u_out, int64_t u_cap, int64_t* n_user, fd_merchant_window* m_out, int64_t m_cap,
+                 int64_t* n_merch) {
   WindowState& w = e.windows;
   CardStore& st = e.state;
   FD_REQUIRE(w.ready, FD_ERR_NOT_LOADED, "windows not initialised (fd_windows_init)");

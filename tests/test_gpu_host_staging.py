@@ -9,7 +9,7 @@ What this adds to the per-feature tests (which drive the same entry points again
                       `present` mask with a model absent
   growth and reuse    n = 65, 1, 300, 7 on one new engine: the staging buffer grows between calls
   n = 0               success, nothing written
-  bad arguments       the codes and fd_last_error texts of csrc/engine.hip, unchanged
+  bad arguments       the codes and fd_last_error texts of csrc/engine.hip and the schedulers it calls (csrc/score.hip), unchanged
 The device call gets its arrays as views that start one element into their allocation, so it does not see the
 allocator's alignment either.
 """

@@ -1,4 +1,4 @@
-"""GPU: the native N >= 2 sharded step (fd_sharded_step, csrc/comm.hip + engine.hip) executed with 2, 4 and 8 ranks
+"""GPU: the native N >= 2 sharded step (fd_sharded_step, csrc/comm.hip sharded_step) executed with 2, 4 and 8 ranks
 (8: the node size BASELINE configs[3] names) on the test box's one GPU, checked against the CPU oracle chain over the global arrival order.
 
 RCCL refuses two ranks on one device, so the ranks here are threads of one process, each driving its own engine
