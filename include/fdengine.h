@@ -1374,6 +1374,8 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    "mlp_launches" (launches of the MLP head's kernel), "graph_steps" (fd_graph_step_* calls with n > 0),
    "text_calls" (fd_text_features_device / _host calls with n > 0), "text_nonascii_rows" (rows those calls flagged
    FD_TEXT_NONASCII; reading it waits for the engine stream),
+   "device_bytes_live" (bytes of device memory the library holds now, over every engine of the process: it falls
+   back to its earlier value when an engine is destroyed, and reads the same through any engine),
    "pipelined_slot_stream_batches" (of those, with the slot pass on
    its own stream), "pipelined_host_ns" (host nanoseconds inside fd_score_batch_pipelined), "sharded_steps" (fd_sharded_step calls), "rccl_ops" (RCCL operations the exchanges issued: sends, receives,
    all-gathers) and "sharded_host_ns_<phase>" (host

@@ -277,11 +277,6 @@ void ab_clear(Engine& e, int id) {
   FD_HIP(hipMemsetAsync(state_of(e, id), 0, sizeof(fd_ab_state), e.stream));
 }
 
-void ab_release(Engine& e) {
-  for (DeviceBuffer* b : {&e.ab.state, &e.ab.partials, &e.ab.part, &e.ab.index, &e.ab.rows}) b->release();
-  for (AbTest& t : e.ab.tests) t.live = false;
-}
-
 void ab_assign(Engine& e, int id, const uint64_t* d_keys, int64_t n, uint8_t* d_variant) {
   const AbTest& t = ab_test(e, id);
   FD_REQUIRE(n >= 0 && n < (1ll << 31), FD_ERR_INVALID_ARG, "batch size out of range");

@@ -180,10 +180,10 @@ void comm_destroy(Engine& e) {
   c.fwd = c.back = nullptr;
   if (!drained) {
     if (!fwd_drained) c.x_fwd = nullptr;  // a stream still running work is not destroyed either
-    for (int s = 0; s < 2; ++s) c.rec[s].ptr = c.cnt[s].ptr = nullptr, c.h_cnt[s] = nullptr;
-    for (int q = 0; q < ShardComm::kInbox; ++q) c.inbox[q].ptr = c.res[q].ptr = nullptr;
-    c.back_buf.ptr = nullptr;
-    c.route_blk.ptr = nullptr;
+    for (int s = 0; s < 2; ++s) c.rec[s].abandon(), c.cnt[s].abandon(), c.h_cnt[s] = nullptr;
+    for (int q = 0; q < ShardComm::kInbox; ++q) c.inbox[q].abandon(), c.res[q].abandon();
+    c.back_buf.abandon();
+    c.route_blk.abandon();
   }
   for (int s = 0; s < 2; ++s) {
     for (auto* b : {&c.rec[s], &c.cnt[s]}) b->release();

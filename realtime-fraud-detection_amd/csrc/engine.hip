@@ -1,6 +1,8 @@
 // engine.hip — C-ABI surface of libfdengine.so (declared in include/fdengine.h), and nothing else: an entry point
 // locks the engine, checks its arguments, stages host arrays where it takes them, and makes one call into the
 // translation unit that does the work (the scoring schedulers: score.hip; the sharded step: comm.hip).
+// Device memory is not released here by name: fd_engine_destroy deletes the engine, ~Engine (below) does the teardown
+// whose order matters, and every DeviceBuffer goes with the struct or the scope that owns it (fd_internal.h).
 // Every entry point catches everything: status codes + a thread-local message cross the ABI,
 // exceptions never do (mirrors the reference's log-and-raise contract, ml/models/model_manager.py:302-307,
 // with the raise done by the Python shim).
@@ -38,6 +40,23 @@ Engine::Timed* Engine::next_event_pair(int kind) {
   t->kind = kind;
   t->split = false;
   return t;
+}
+
+// Only what has an order: the communicators go while every buffer is still there (comm_destroy decides which of them
+// an undrained exchange may still touch, and abandons those), the streams are drained before they are destroyed, and
+// all of it before the members' destructors free the device memory. Nothing here throws.
+Engine::~Engine() {
+  if (stream) (void)hipStreamSynchronize(stream);
+  try {
+    comm_destroy(*this);
+  } catch (...) {
+  }
+  pipe.release();
+  side.release();
+  for (auto& ev : events)
+    for (hipEvent_t h : {ev.a, ev.b, ev.c, ev.d})
+      if (h) (void)hipEventDestroy(h);
+  if (own_stream) (void)hipStreamDestroy(own_stream);
 }
 
 }  // namespace fd
@@ -146,63 +165,7 @@ int fd_engine_destroy(fd_engine* eng) {
     FD_REQUIRE(ok, FD_ERR_HIP, "engine leaked: streams still busy " + std::to_string(e.comm.timeout_ms) +
                                    " ms after the communicators were aborted (" + e.comm.abort_reason + ")");
   }
-  (void)hipStreamSynchronize(e.stream);
-  for (auto& f : e.forests) {
-    for (auto* b : {&f.split.bins, &f.split.nan, &f.split.leaves}) b->release();
-    f.blob.release();
-    f.leaf_ids.release();
-    f.b_blob.release();
-    f.b_thr.release();
-    f.b_thr_off.release();
-    fd::shap_forget(f);
-  }
-  e.shap_partial.release();
-  fd::gbdt_release(e);
-  fd::iforest_fit_release(e);
-  e.stage.release();
-  e.scratch_probs.release();
-  e.feat_vec.release();
-  fd::windows_release(e);
-  fd::sink_release(e);
-  fd::graph_release(e);
-  fd::text_release(e);
-  fd::ab_release(e);
-  fd::metrics_release(e);
-  for (auto* b : {&e.route_blk, &e.route_blk_stream, &e.route_out, &e.route_err, &e.seq_buf, &e.seq_desc, &e.lstm.wpk, &e.lstm.wpk4, &e.lstm.bias,
-                  &e.lstm.wout, &e.lstm.bout, &e.state.seq, &e.mlp.blob})
-    b->release();
-  e.side.release();
-  try {
-    fd::comm_destroy(e);
-  } catch (...) {
-  }
-  e.pipe.release();
-  for (auto* b : {&e.state.uext, &e.state.mext, &e.state.vocab, &e.feat_ext}) b->release();
-  for (auto& P1 : e.ens1)
-    for (auto* b : {&P1.nodes[0], &P1.nodes[1], &P1.thr}) b->release();
-  for (auto* b : {&e.ens.nodes[0], &e.ens.nodes[1], &e.ens.thr})
-    b->release();
-  {  // ingest codec tables
-    fd::IngestTables& t = e.ingest;
-    for (auto* b : {&t.mkeys, &t.mvals}) b->release();
-    for (int w = 0; w < 3; ++w) {
-      t.vkeys[w].release();
-      t.vvals[w].release();
-    }
-  }
-  for (auto* b : {&e.state.pages, &e.state.keys, &e.state.merchants, &e.state.err, &e.state.sat,
-                  &e.state.bucket_scr})
-    b->release();
-  for (auto& g : e.state.gs)
-    for (auto* b : {&g.slot, &g.bucket_fill, &g.pairs, &g.ovf_cnt, &g.ovf_key, &g.ovf_b, &g.prep}) b->release();
-  for (auto& ev : e.events) {
-    (void)hipEventDestroy(ev.a);
-    (void)hipEventDestroy(ev.b);
-    if (ev.c) (void)hipEventDestroy(ev.c);
-    if (ev.d) (void)hipEventDestroy(ev.d);
-  }
-  if (e.own_stream) (void)hipStreamDestroy(e.own_stream);
-  delete eng;
+  delete eng;  // ~Engine: the ordered teardown, then every buffer with its owner
   FD_API_END
 }
 
@@ -316,6 +279,9 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
     *value = (int64_t)e.pipe.host_ns;
   } else if (k == "pipelined_slot_stream_batches") {  // of those: the slot pass on its own stream (slot_stream)
     *value = (int64_t)e.pipe.slot_stream_total;
+  } else if (k == "device_bytes_live") {  // bytes of device memory the library holds now, over every engine of the
+    // process (DeviceBuffer; memory abandoned behind an undrained exchange stays counted)
+    *value = (int64_t)fd::g_device_bytes_live.load();
   } else if (k == "window_saturated") {  // sliding windows: transactions whose 24 h window held K prior events
     // (its count may be truncated at the ring capacity); synchronises the engine's streams
     FD_REQUIRE(e.state.ready, FD_ERR_NOT_LOADED, "card state not initialised (fd_state_init)");
@@ -771,15 +737,8 @@ int fd_unload_forest(fd_engine* eng, int slot) {
   Engine& e = E(eng);
   fd::PackedForest& pf = slot_of(e, slot);
   FD_HIP(hipStreamSynchronize(e.stream));
-  pf.blob.release();
-  pf.leaf_ids.release();
-  pf.b_blob.release();
-  pf.b_thr.release();
-  pf.b_thr_off.release();
-  for (auto* b : {&pf.split.bins, &pf.split.nan, &pf.split.leaves}) b->release();
-  for (auto* b : {&pf.sp.nodes, &pf.sp.leaf_val, &pf.sp.leaf_ids}) b->release();
-  pf.sp.gen = 0;
-  fd::shap_forget(pf);
+  pf.drop_device();
+  fd::shap_forget(pf);  // the covers
   pf.sparse_only = false;
   pf.binned = false;
   pf.loaded = false;

@@ -14,6 +14,8 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "fdengine.h"
@@ -107,16 +109,36 @@ void set_error(const std::string& msg);
     if (!(cond)) throw ::fd::Error((code), (msg)); \
   } while (0)
 
-// Device allocation owned by the engine; grows, never shrinks.
+// bytes held through DeviceBuffer in this process, every engine together (counter "device_bytes_live")
+inline std::atomic<long long> g_device_bytes_live{0};
 
+// A device allocation and its owner: grows, never shrinks, freed when the owner goes (a member with its struct, a
+// local at scope exit — an exception's included). Moves, never copies. The only hipMalloc / hipFree of the library.
 struct DeviceBuffer {
   void* ptr = nullptr;
   size_t bytes = 0;
+  DeviceBuffer() = default;
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  DeviceBuffer(DeviceBuffer&& o) noexcept { swap(o); }
+  DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
+    if (this != &o) {
+      release();
+      swap(o);
+    }
+    return *this;
+  }
+  ~DeviceBuffer() { release(); }
+  void swap(DeviceBuffer& o) noexcept {
+    std::swap(ptr, o.ptr);
+    std::swap(bytes, o.bytes);
+  }
   void ensure(size_t need) {
     if (need <= bytes) return;
     release();
     FD_HIP(hipMalloc(&ptr, need));
     bytes = need;
+    g_device_bytes_live.fetch_add((long long)need, std::memory_order_relaxed);
   }
   // grow by a quarter more than asked: buffers sized per batch by a count that wanders (a shard's inbox) then
   // reallocate O(log) times instead of at every new maximum (hipFree waits for the device)
@@ -125,12 +147,19 @@ struct DeviceBuffer {
   }
   void release() {
     if (ptr) (void)hipFree(ptr);
+    g_device_bytes_live.fetch_sub((long long)bytes, std::memory_order_relaxed);
+    ptr = nullptr;
+    bytes = 0;
+  }
+  // drop the allocation without freeing it: a deliberate leak of memory the device may still touch (it stays counted)
+  void abandon() {
     ptr = nullptr;
     bytes = 0;
   }
   template <class T>
   T* as() const { return static_cast<T*>(ptr); }
 };
+static_assert(!std::is_copy_constructible_v<DeviceBuffer> && std::is_nothrow_move_constructible_v<DeviceBuffer>);
 
 // small-batch tree-split scratch of one forest (forest.hip launch_split)
 struct SplitScratch {
@@ -233,6 +262,13 @@ struct PackedForest {
   // table built from them; both go with the forest (shap_forget)
   std::vector<double> t_cover;
   mutable ShapImage shap;
+  // every device image of the forest freed (unload); the host copy of the trees stays
+  void drop_device() {
+    for (DeviceBuffer* b : {&blob, &leaf_ids, &b_blob, &b_thr, &b_thr_off, &n_blob, &n_leaves, &split.bins, &split.nan,
+                            &split.leaves, &sp.nodes, &sp.leaf_val, &sp.leaf_ids, &shap.paths, &shap.elems})
+      b->release();
+    sp.gen = shap.gen = 0;
+  }
 };
 
 // iforest_fit.hip: device buffers of a fit (they grow and stay), the grown forest packed for the offset's scoring pass
@@ -836,7 +872,7 @@ struct Pipeline {
   bool copy_vec[kSlots] = {};  // that copy also read the slot's vectors (the slot's next features wait)
   // first use: the streams (option stream_priority) and events; slot_mode -1 resolved by the card table's size
   void create(int stream_prio, bool big_table);
-  void release();  // streams drained and destroyed, events destroyed, buffers freed
+  void release();  // streams drained and destroyed, events destroyed (~Engine)
   // stream s after the scoring of every pipelined batch so far (a new engine stream inherits the old one's order)
   void order_after_scoring(hipStream_t s);
 };
@@ -922,6 +958,7 @@ struct Engine {
   size_t events_used = 0;
   void activate() const { FD_HIP(hipSetDevice(device)); }
   Timed* next_event_pair(int kind);
+  ~Engine();  // engine.hip: the teardown whose order matters; the buffers then go with their owners
 };
 
 // forest.hip
@@ -988,7 +1025,6 @@ void windows_init(Engine& e, const fd_window_params& p);
 void windows_step(Engine& e, const fd_txn_batch& t, const fd_window_inputs& in, int64_t n, bool flush,
                   fd_user_window* u_out, int64_t u_cap, int64_t* n_user, fd_merchant_window* m_out, int64_t m_cap,
                   int64_t* n_merch, bool timed = false);  // timed: an FD_TIMING_WINDOWS event pair around the step
-void windows_release(Engine& e);
 void windows_observe(Engine& e, int64_t max_event_ts);
 void merchant_windows_merge(const fd_merchant_window* p, int64_t n, fd_merchant_window* out, int64_t* n_out);
 // ingest.hip
@@ -1000,7 +1036,6 @@ void sink_init(Engine& e, const fd_sink_params& p);
 void sink_update(Engine& e, const fd_txn_batch& t, const fd_window_inputs& in, int64_t n);
 void sink_query(Engine& e, int kind, const int64_t* bucket, const int32_t* merchant, int64_t n, fd_aggregate* out);
 void sink_evict_before(Engine& e, int64_t hour, int64_t* kept_entries, int64_t* kept_users);
-void sink_release(Engine& e);
 // snapshot.hip
 void state_snapshot(Engine& e, const char* path, int shard, int n_shards, int64_t* bytes_written);
 void state_restore(Engine& e, const char* path, int shard, int n_shards, int flags, int64_t* cards_restored);
@@ -1109,11 +1144,9 @@ void launch_mlp(Engine& e, hipStream_t stream, const float* d_X, int64_t n, int3
 // graph.hip
 void graph_init(Engine& e, const fd_graph_params& p);
 void graph_clear(Engine& e);
-void graph_release(Engine& e);
 void graph_info(Engine& e, int64_t* total, int64_t* held);
 void graph_step(Engine& e, const fd_txn_batch& t, int64_t n, double* d_out);  // device pointers, on e.stream
 // text.hip
-void text_release(Engine& e);
 int64_t text_nonascii_rows(Engine& e);  // waits for the engine stream
 void text_features(Engine& e, const uint8_t* d_bytes, const int64_t* d_off, int64_t n, double* d_feat,
                    uint8_t* d_patterns, uint8_t* d_status);  // device pointers, on e.stream; outputs may be null
@@ -1122,7 +1155,6 @@ const AbTest& ab_test(Engine& e, int id);  // FD_ERR_NOT_LOADED unless created
 void ab_create(Engine& e, int id, const fd_ab_params& p);
 void ab_destroy(Engine& e, int id);
 void ab_clear(Engine& e, int id);
-void ab_release(Engine& e);
 void ab_assign(Engine& e, int id, const uint64_t* d_keys, int64_t n, uint8_t* d_variant);
 void ab_partition(Engine& e, const uint8_t* d_variant, int64_t n, int32_t* d_idx, int64_t* d_counts);
 void ab_gather_rows(Engine& e, const float* d_X, const int32_t* d_idx, int64_t n, int32_t ld, float* d_Xp);
@@ -1137,7 +1169,6 @@ void metrics_check_params(const fd_metrics_params& p);  // FD_ERR_INVALID_ARG
 void metrics_live(Engine& e);                           // FD_ERR_NOT_LOADED before metrics_init
 void metrics_init(Engine& e, const fd_metrics_params& p);
 void metrics_clear(Engine& e);
-void metrics_release(Engine& e);
 void metrics_check_record(const MetricsHeader& h, const void* fraud_prob, const void* decision,
                           const void* model_probs, int32_t n_models, double timestamp, int64_t n);
 void metrics_record(Engine& e, const double* d_fraud_prob, const uint8_t* d_decision, const double* d_model_probs,
@@ -1185,7 +1216,6 @@ void gbdt_fit_device(Engine& e, const float* d_X, const uint8_t* d_y, int64_t n,
 // the same with the matrix also on the host (h_X: the cuts are computed from it without a copy back)
 void gbdt_fit_staged(Engine& e, const float* d_X, const float* h_X, const uint8_t* d_y, int64_t n, int32_t ld,
                      int32_t F, const fd_gbdt_params& p, const fd_gbdt_model& out, int64_t* n_nodes, float* d_margins);
-void gbdt_release(Engine& e);
 
 // iforest_fit.hip: the IsolationForest fit (include/fdengine.h "training: IsolationForest"; the rule is
 // iforest_fit_row.h). Host pointers unless named d_*; the outputs are host arrays.
@@ -1207,7 +1237,6 @@ void iforest_fit_grow_tree_ref_host(const float* X, int64_t n, int32_t ld, int32
 void iforest_fit_grow_tree_device(Engine& e, const float* d_X, int64_t n, int32_t ld, int32_t F, const int32_t* rows,
                                   int32_t m, uint64_t feature_mask, const fd_iforest_fit_params& p, int32_t tree,
                                   fd_tree_arrays& out, double* n_node_samples, int64_t* n_nodes);
-void iforest_fit_release(Engine& e);
 // shap.hip: path-dependent TreeSHAP (include/fdengine.h "forest attribution")
 struct ShapTable {
   std::vector<fd_shap_path> paths;

@@ -1984,7 +1984,6 @@ int64_t state_count(Engine& e) {
   unsigned long long c = 0;
   FD_HIP(hipMemcpyAsync(&c, tmp.ptr, 8, hipMemcpyDeviceToHost, e.stream));
   FD_HIP(hipStreamSynchronize(e.stream));
-  tmp.release();
   return (int64_t)c;
 }
 

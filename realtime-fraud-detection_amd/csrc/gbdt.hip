@@ -710,9 +710,4 @@ void gbdt_fit_staged(Engine& e, const float* d_X, const float* h_X, const uint8_
   fit_device(e, d_X, h_X, d_y, n, ld, F, p, out, n_nodes, d_margins);
 }
 
-void gbdt_release(Engine& e) {
-  GbdtScratch& s = e.gbdt;
-  for (auto* b : {&s.bins, &s.gh, &s.mask, &s.pos, &s.margin, &s.hist, &s.nodes, &s.cuts, &s.offsets}) b->release();
-}
-
 }  // namespace fd

@@ -381,12 +381,6 @@ void graph_clear(Engine& e) {
   g.base = 0;
 }
 
-void graph_release(Engine& e) {
-  for (DeviceBuffer& b : e.graph.log) b.release();
-  e.graph.dm.release();
-  e.graph.ready = false;
-}
-
 void graph_info(Engine& e, int64_t* total, int64_t* held) {
   const GraphState& g = e.graph;
   FD_REQUIRE(g.ready, FD_ERR_NOT_LOADED, "graph log not initialised (fd_graph_init)");

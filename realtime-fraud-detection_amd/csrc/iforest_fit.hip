@@ -516,14 +516,4 @@ void iforest_fit_device(Engine& e, const float* d_X, int64_t n, int32_t ld, int3
   for (auto* v : {&pf.t_threshold, &pf.t_leaf}) std::vector<double>().swap(*v);
 }
 
-void iforest_fit_release(Engine& e) {
-  IForestFitScratch& s = e.iforest;
-  for (auto* b : {&s.rows, &s.masks, &s.heaps, &s.raw, &s.prob, &s.sorted, &s.sort_tmp}) b->release();
-  PackedForest& f = s.scorer;
-  for (auto* b : {&f.split.bins, &f.split.nan, &f.split.leaves, &f.blob, &f.leaf_ids, &f.b_blob, &f.b_thr, &f.b_thr_off,
-                  &f.n_blob, &f.n_leaves, &f.sp.nodes, &f.sp.leaf_val, &f.sp.leaf_ids})
-    b->release();
-  shap_forget(f);
-}
-
 }  // namespace fd

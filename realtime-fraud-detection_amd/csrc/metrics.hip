@@ -200,11 +200,6 @@ void metrics_clear(Engine& e) {
   FD_HIP(hipMemsetAsync(dev_state(e), 0, metrics_state_bytes(h.slots), e.stream));
 }
 
-void metrics_release(Engine& e) {
-  for (DeviceBuffer* b : {&e.metrics.state, &e.metrics.partials, &e.metrics.summary}) b->release();
-  e.metrics.live = false;
-}
-
 // the checks every form of a record call makes before anything is queued or staged
 void metrics_check_record(const MetricsHeader& h, const void* fraud_prob, const void* decision,
                           const void* model_probs, int32_t n_models, double timestamp, int64_t n) {

@@ -433,17 +433,11 @@ void Pipeline::release() {
       (void)hipStreamDestroy(st);
     }
   if (entry_ev) (void)hipEventDestroy(entry_ev);
-  for (int k = 0; k < kSlots; ++k) {
+  for (int k = 0; k < kSlots; ++k)
     for (hipEvent_t ev : {slot_ev[k], feat_ev[k], copy_ev[k]})
       if (ev) (void)hipEventDestroy(ev);
-    vec[k].release();
-    out[k].release();
-    seq[k].release();
-  }
-  for (int k = 0; k < kSplitRing; ++k) {
-    if (done_ev[k]) (void)hipEventDestroy(done_ev[k]);
-    split[k].release();
-  }
+  for (hipEvent_t ev : done_ev)
+    if (ev) (void)hipEventDestroy(ev);
 }
 
 void Pipeline::order_after_scoring(hipStream_t s) {

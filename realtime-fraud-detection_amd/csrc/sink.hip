@@ -254,8 +254,6 @@ void sink_query(Engine& e, int kind, const int64_t* bucket, const int32_t* merch
   FD_HIP(hipGetLastError());
   FD_HIP(hipMemcpyAsync(out, dout.ptr, (size_t)n * sizeof(fd_aggregate), hipMemcpyDeviceToHost, e.stream));
   FD_HIP(hipStreamSynchronize(e.stream));
-  dk.release();
-  dout.release();
 }
 
 void sink_evict_before(Engine& e, int64_t hour, int64_t* kept_entries, int64_t* kept_users) {
@@ -280,21 +278,10 @@ void sink_evict_before(Engine& e, int64_t hour, int64_t* kept_entries, int64_t* 
   unsigned long long c[2] = {0, 0};
   FD_HIP(hipMemcpyAsync(c, cnt.ptr, 16, hipMemcpyDeviceToHost, e.stream));
   sink_check(e);
-  std::swap(k.table.ptr, nt.ptr);
-  std::swap(k.users.ptr, nu.ptr);
-  nt.release();
-  nu.release();
-  cnt.release();
+  k.table.swap(nt);  // the old tables go with the locals
+  k.users.swap(nu);
   if (kept_entries) *kept_entries = (int64_t)c[0];
   if (kept_users) *kept_users = (int64_t)c[1];
-}
-
-void sink_release(Engine& e) {
-  SinkState& k = e.sink;
-  k.table.release();
-  k.users.release();
-  k.err.release();
-  k.ready = false;
 }
 
 }  // namespace fd

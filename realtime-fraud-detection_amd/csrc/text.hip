@@ -208,11 +208,6 @@ __global__ void __launch_bounds__(kTextThreads) text_finish_kernel(const int64_t
 
 }  // namespace
 
-void text_release(Engine& e) {
-  e.text.acc.release();
-  e.text.count.release();
-}
-
 int64_t text_nonascii_rows(Engine& e) {
   if (!e.text.count.ptr) return 0;
   unsigned long long v = 0;

@@ -568,12 +568,4 @@ void merchant_windows_merge(const fd_merchant_window* p, int64_t n, fd_merchant_
   *n_out = m;
 }
 
-void windows_release(Engine& e) {
-  WindowState& w = e.windows;
-  for (auto* b : {&w.ulog[0], &w.ulog[1], &w.mlog[0], &w.mlog[1], &w.keys, &w.vals, &w.sort_tmp, &w.uout, &w.mout,
-                  &w.scalars})
-    b->release();
-  w.ready = false;
-}
-
 }  // namespace fd

@@ -68,7 +68,8 @@ class FraudEngine:
         N.call("fd_engine_set_option", self._h, key.encode(), int(value))
 
     def counter(self, key: str) -> int:
-        """fd_engine_get_counter: "pipelined_batches", "sharded_steps", "sharded_host_ns_<phase>" (include/fdengine.h)."""
+        """fd_engine_get_counter: "pipelined_batches", "sharded_steps", "sharded_host_ns_<phase>", "device_bytes_live"
+        (device memory the library holds now, every engine of the process together) ... (include/fdengine.h)."""
         v = N._i64()
         N.call("fd_engine_get_counter", self._h, key.encode(), C.byref(v))
         return int(v.value)
