@@ -429,6 +429,67 @@ int fd_gbdt_fit_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n
 int fd_gbdt_fit_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F,
                          const fd_gbdt_params* params, fd_gbdt_model* out, int64_t* n_nodes, float* margins);
 
+/* The fit watched on a held-out set (XGBClassifier.fit(..., eval_set=[(X_test, y_test)]), model_trainer.py:83-96),
+   with early stopping and a class weight. Rules (csrc/gbdt_row.h, DESIGN §4.14 "Evaluation"):
+   Class weight: with scale_pos_weight = w a positive row's g = quantise(w (p - 1)), h = max(1, quantise(w p (1 - p)));
+   negative rows are unchanged; w == 1 gives the bits of fd_gbdt_fit_*. 0 < w <= 64 (FD_ERR_INVALID_ARG) and
+   n max(1, w) <= 2^28 (FD_ERR_UNSUPPORTED above). Evaluation is not weighted.
+   Eval margins: the eval matrix is binned with the training cuts; after round t every eval row adds tree t's leaf to
+   its f32 margin (from the base margin, in tree order: what fd_forest_predict_* reports as raw).
+   AUC: key(m) is a u32 ordered like the f32 margin, -0 and +0 equal, every NaN one key above +inf's. With P / N the
+   eval set's positives / negatives, 2U = sum over positive rows of #{negatives with key < its key} + #{negatives with
+   key <= its key}; auc = (double)(2U) / (double)(2 P N). Error: #{rows with (margin > 0) != y} / n. Both are an
+   integer count and one division: the bits do not depend on the launch shape.
+   Stopping (early_stopping_rounds = k > 0): round t improves iff its metric is strictly better (AUC: greater, error:
+   less) than the best so far, round 0 always; after k consecutive rounds without improvement the fit stops:
+   rounds_run = best_iteration + k + 1, else n_rounds. Every grown tree is returned (rounds_run trees: tree_offsets[0
+   .. rounds_run] are written): truncating to best_iteration + 1 trees is the caller's choice. */
+#define FD_GBDT_METRIC_AUC 0
+#define FD_GBDT_METRIC_ERROR 1
+typedef struct {
+  /* in */
+  const float* X;    /* n x ld f32 eval rows (ld >= F); NULL or n == 0: no eval set, only the class weight acts */
+  const uint8_t* y;  /* n labels, 0 / 1 */
+  int64_t n;
+  int32_t ld;
+  int32_t metric;                /* FD_GBDT_METRIC_* */
+  int32_t early_stopping_rounds; /* 0: none; > 0 needs an eval set */
+  int32_t reserved;
+  double scale_pos_weight; /* (0, 64] */
+  /* out (each may be NULL) */
+  double* metric_out;  /* n_rounds: the first rounds_run entries are written (always host memory) */
+  float* margins;      /* n: the eval margins after the last round that ran */
+  float* best_margins; /* the fit's n rows: the training margins after tree best_iteration */
+  int32_t rounds_run;
+  int32_t best_iteration; /* -1 without an eval set */
+} fd_gbdt_eval;
+
+/* As fd_gbdt_fit_* (the same two calls; eval is not read by the first), watched as `eval` says. _device: eval->X, y,
+   margins and best_margins are device pointers too. The loop still issues launches only: per round the eval walk, for
+   AUC a radix sort, a scan and a count, and a one-thread kernel that writes metric_out[t] and applies the stopping
+   rule to a state on the device; once it stops, the fit's own kernels of later rounds return at once, and the curve,
+   rounds_run and best_iteration come back in the one copy at the end. FD_ERR_INVALID_ARG: early stopping without an
+   eval set; eval->ld < F; an unknown metric; for AUC an eval set of one class ("Only one class present in y_true. ROC
+   AUC score is not defined in that case."; _host and _ref_host check, _device trusts its caller). Counters
+   "gbdt_eval_launches", "gbdt_rounds_run"; "gbdt_trees" and "gbdt_hist_launches" advance by the rounds that ran. */
+int fd_gbdt_fit_eval_device(fd_engine* eng, const float* d_X, const uint8_t* d_y, int64_t n, int32_t ld, int32_t F,
+                            const fd_gbdt_params* params, fd_gbdt_eval* eval, fd_gbdt_model* out, int64_t* n_nodes,
+                            float* d_margins);
+int fd_gbdt_fit_eval_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F,
+                          const fd_gbdt_params* params, fd_gbdt_eval* eval, fd_gbdt_model* out, int64_t* n_nodes,
+                          float* margins);
+int fd_gbdt_fit_eval_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F,
+                              const fd_gbdt_params* params, fd_gbdt_eval* eval, fd_gbdt_model* out, int64_t* n_nodes,
+                              float* margins);
+/* The metric of caller margins (n f32) and labels: the sort and count path of the fit on its own. _host runs the
+   kernels, _ref_host plain C++. FD_ERR_INVALID_ARG: n < 1, a label other than 0 / 1, one class only for AUC. */
+int fd_gbdt_metric_host(fd_engine* eng, const float* margins, const uint8_t* y, int64_t n, int32_t metric,
+                        double* out);
+int fd_gbdt_metric_ref_host(const float* margins, const uint8_t* y, int64_t n, int32_t metric, double* out);
+/* fd_gbdt_grad_ref_host under the class weight: the pairs the watched fit's rounds compute (plain C++) */
+int fd_gbdt_grad_weighted_ref_host(const float* margin, const uint8_t* y, int64_t n, double scale_pos_weight,
+                                   int32_t* g, int32_t* h);
+
 /* ---------------------------------------------------------------- training: IsolationForest (ModelTrainer) */
 /* Replaces ModelTrainer.train_isolation_forest's fit (ml/training/model_trainer.py:235-276): grows the trees of a
    scikit-learn IsolationForest (ExtraTreeRegressor(splitter="random", max_features=1) on max_samples rows drawn
@@ -1369,6 +1430,10 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    "forest_shap_launches" (launches of the TreeSHAP kernel, fd_forest_shap_*),
    "gbdt_hist_launches" (launches of the GBDT fit's histogram kernel: one per tree level), "gbdt_trees" (trees grown
    on the device by fd_gbdt_fit_* / fd_gbdt_grow_tree_*), "gbdt_nodes_split" (split nodes of those trees),
+   "gbdt_eval_launches" (launches of the GBDT fit's eval kernel that walked a tree: one per round that ran with an
+   eval set), "gbdt_rounds_run" (rounds the device fits ran; of a fit that
+   stopped early, the launches that returned at the stop flag count in neither this, "gbdt_trees", "gbdt_hist_launches"
+   nor "gbdt_eval_launches"),
    "iforest_fit_trees" (IsolationForest trees grown on the device by fd_iforest_fit_device / _host /
    _grow_tree_host), "iforest_fit_nodes_split" (split nodes of those trees),
    "mlp_launches" (launches of the MLP head's kernel), "graph_steps" (fd_graph_step_* calls with n > 0),

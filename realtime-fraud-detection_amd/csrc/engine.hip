@@ -255,6 +255,10 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
     *value = (int64_t)e.gbdt.trees;
   } else if (k == "gbdt_nodes_split") {  // split nodes of those trees
     *value = (int64_t)e.gbdt.nodes_split;
+  } else if (k == "gbdt_eval_launches") {  // launches of the eval kernel that walked a tree (a watched fit's rounds)
+    *value = (int64_t)e.gbdt.eval_launches;
+  } else if (k == "gbdt_rounds_run") {  // rounds the device fits ran (launches that returned at the stop flag excluded)
+    *value = (int64_t)e.gbdt.rounds_run;
   } else if (k == "iforest_fit_trees") {  // IsolationForest trees grown on the device (fd_iforest_fit_*)
     *value = (int64_t)e.iforest.trees;
   } else if (k == "iforest_fit_nodes_split") {  // split nodes of those trees
@@ -1135,6 +1139,125 @@ int fd_gbdt_fit_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n
   st.upload();
   fd::gbdt_fit_staged(e, dX, n ? X : &none, dy, n, ld, F, *params, *out, n_nodes, dm);
   st.download();
+  FD_API_END
+}
+
+int fd_gbdt_fit_eval_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F,
+                              const fd_gbdt_params* params, fd_gbdt_eval* eval, fd_gbdt_model* out, int64_t* n_nodes,
+                              float* margins) {
+  FD_API_BEGIN
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "gbdt: null params");
+  if (!out) {
+    gbdt_capacity(*params, n, F, n_nodes);
+    return FD_OK;
+  }
+  FD_REQUIRE(eval, FD_ERR_INVALID_ARG, "gbdt: null eval");
+  FD_REQUIRE(n == 0 || (X && y), FD_ERR_INVALID_ARG, "gbdt: null X / y");
+  fd::gbdt_fit_ref_host(X, y, n, ld, F, *params, *out, n_nodes, margins, eval);
+  FD_API_END
+}
+
+int fd_gbdt_fit_eval_device(fd_engine* eng, const float* d_X, const uint8_t* d_y, int64_t n, int32_t ld, int32_t F,
+                            const fd_gbdt_params* params, fd_gbdt_eval* eval, fd_gbdt_model* out, int64_t* n_nodes,
+                            float* d_margins) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "gbdt: null params");
+  if (!out) {
+    gbdt_capacity(*params, n, F, n_nodes);
+    return FD_OK;
+  }
+  FD_REQUIRE(eval, FD_ERR_INVALID_ARG, "gbdt: null eval");
+  FD_REQUIRE(n == 0 || (d_X && d_y), FD_ERR_INVALID_ARG, "gbdt: null X / y");
+  fd::gbdt_fit_eval_device(e, d_X, nullptr, d_y, n, ld, F, *params, *eval, *out, n_nodes, d_margins);
+  FD_API_END
+}
+
+int fd_gbdt_fit_eval_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F,
+                          const fd_gbdt_params* params, fd_gbdt_eval* eval, fd_gbdt_model* out, int64_t* n_nodes,
+                          float* margins) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "gbdt: null params");
+  if (!out) {
+    gbdt_capacity(*params, n, F, n_nodes);
+    return FD_OK;
+  }
+  FD_REQUIRE(eval, FD_ERR_INVALID_ARG, "gbdt: null eval");
+  fd::gbdt_check_params(*params, n, F, true);
+  FD_REQUIRE(n == 0 || (X && y), FD_ERR_INVALID_ARG, "gbdt: null X / y");
+  FD_REQUIRE(ld >= F, FD_ERR_INVALID_ARG, "gbdt: ld < F");
+  const bool watched = fd::gbdt_check_eval(*eval, n, F, true);
+  for (int64_t i = 0; i < n; ++i) FD_REQUIRE(y[i] <= 1, FD_ERR_INVALID_ARG, "gbdt: labels must be 0 or 1");
+  const float none = 0.0f;
+  const uint8_t zero = 0;
+  Stage st(e);
+  const float *dX, *deX = nullptr;
+  const uint8_t *dy, *dey = nullptr;
+  float *dm, *dem = nullptr, *dbm = nullptr;
+  st.in(dX, n ? X : &none, std::max<size_t>((size_t)n * ld, 1));
+  st.in(dy, n ? y : &zero, std::max<size_t>((size_t)n, 1));
+  st.out(dm, margins, (size_t)n);
+  if (watched) {
+    st.in(deX, eval->X, (size_t)eval->n * eval->ld);
+    st.in(dey, eval->y, (size_t)eval->n);
+    st.out(dem, eval->margins, (size_t)eval->n);
+    st.out(dbm, eval->best_margins, (size_t)n);
+  }
+  st.upload();
+  fd_gbdt_eval dev = *eval;  // the same arguments with the staged pointers
+  dev.X = deX;
+  dev.y = dey;
+  dev.margins = dem;
+  dev.best_margins = dbm;
+  fd::gbdt_fit_eval_device(e, dX, n ? X : &none, dy, n, ld, F, *params, dev, *out, n_nodes, dm);
+  st.download();
+  eval->rounds_run = dev.rounds_run;
+  eval->best_iteration = dev.best_iteration;
+  FD_API_END
+}
+
+int fd_gbdt_metric_ref_host(const float* margins, const uint8_t* y, int64_t n, int32_t metric, double* out) {
+  FD_API_BEGIN
+  FD_REQUIRE(n >= 1 && margins && y && out, FD_ERR_INVALID_ARG, "gbdt: the metric needs margins, labels and n >= 1");
+  FD_REQUIRE(metric == FD_GBDT_METRIC_AUC || metric == FD_GBDT_METRIC_ERROR, FD_ERR_INVALID_ARG,
+             "gbdt: unknown eval metric");
+  FD_REQUIRE(n <= (1ll << 28), FD_ERR_UNSUPPORTED, "gbdt: more than 2^28 eval rows");
+  fd::gbdt_check_metric_labels(y, n, metric);
+  *out = fd::gbdt_metric_ref_host(margins, y, n, metric);
+  FD_API_END
+}
+
+int fd_gbdt_grad_weighted_ref_host(const float* margin, const uint8_t* y, int64_t n, double scale_pos_weight,
+                                   int32_t* g, int32_t* h) {
+  FD_API_BEGIN
+  FD_REQUIRE(n >= 0 && (n == 0 || (margin && y && g && h)), FD_ERR_INVALID_ARG, "gbdt: null margin / y / g / h");
+  FD_REQUIRE(scale_pos_weight > 0.0 && scale_pos_weight <= 64.0, FD_ERR_INVALID_ARG,
+             "gbdt: scale_pos_weight must be in (0, 64]");
+  for (int64_t i = 0; i < n; ++i) FD_REQUIRE(y[i] <= 1, FD_ERR_INVALID_ARG, "gbdt: labels must be 0 or 1");
+  fd::gbdt_grad_weighted_ref_host(margin, y, n, scale_pos_weight, g, h);
+  FD_API_END
+}
+
+int fd_gbdt_metric_host(fd_engine* eng, const float* margins, const uint8_t* y, int64_t n, int32_t metric,
+                        double* out) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(n >= 1 && margins && y && out, FD_ERR_INVALID_ARG, "gbdt: the metric needs margins, labels and n >= 1");
+  FD_REQUIRE(metric == FD_GBDT_METRIC_AUC || metric == FD_GBDT_METRIC_ERROR, FD_ERR_INVALID_ARG,
+             "gbdt: unknown eval metric");
+  FD_REQUIRE(n <= (1ll << 28), FD_ERR_UNSUPPORTED, "gbdt: more than 2^28 eval rows");
+  fd::gbdt_check_metric_labels(y, n, metric);
+  Stage st(e);
+  const float* dm;
+  const uint8_t* dy;
+  st.in(dm, margins, (size_t)n);
+  st.in(dy, y, (size_t)n);
+  st.upload();
+  *out = fd::gbdt_metric_device(e, dm, dy, n, metric);
   FD_API_END
 }
 

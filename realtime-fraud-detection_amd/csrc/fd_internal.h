@@ -195,11 +195,16 @@ struct SparseImage {
 };
 
 // gbdt.hip: device buffers of a fit (they grow and stay), the histogram kernel's rows per workgroup (option
-// "gbdt_hist_rows") and the counters "gbdt_hist_launches" / "gbdt_trees" / "gbdt_nodes_split"
+// "gbdt_hist_rows") and the counters "gbdt_hist_launches" / "gbdt_trees" / "gbdt_nodes_split"; of a watched fit
+// (fd_gbdt_fit_eval_*) the eval rows' bins and margins, their sort words (unsorted, then sorted), the negatives'
+// prefix counts, rocPRIM's temporary storage (asked for once per fit), the stop state, the metric curve and the
+// training margins after the best round; counters "gbdt_eval_launches" / "gbdt_rounds_run"
 struct GbdtScratch {
   DeviceBuffer bins, gh, mask, pos, margin, hist, nodes, cuts, offsets;
+  DeviceBuffer ebins, emargin, words, neg_before, eval_tmp, state, curve, best_margin;
+  size_t eval_tmp_bytes = 0;
   int hist_rows = 4096;
-  unsigned long long hist_launches = 0, trees = 0, nodes_split = 0;
+  unsigned long long hist_launches = 0, trees = 0, nodes_split = 0, eval_launches = 0, rounds_run = 0;
 };
 
 // The TreeSHAP path table of a forest on the device (shap.hip): built on the first explain call, for the
@@ -1200,11 +1205,22 @@ void gbdt_check_params(const fd_gbdt_params& p, int64_t n, int32_t F, bool fit);
 void gbdt_bin_ref_host(const float* X, int64_t n, int32_t ld, int32_t F, const float* cuts, const int32_t* offsets,
                        uint8_t* bins);
 void gbdt_grad_ref_host(const float* margin, const uint8_t* y, int64_t n, int32_t* g, int32_t* h);
+void gbdt_grad_weighted_ref_host(const float* margin, const uint8_t* y, int64_t n, double w, int32_t* g, int32_t* h);
 void gbdt_grow_tree_ref_host(const uint8_t* bins, int64_t n, int32_t F, const float* cuts, const int32_t* offsets,
                              const int32_t* g, const int32_t* h, const uint8_t* row_mask, uint64_t feature_mask,
                              const fd_gbdt_params& p, const fd_gbdt_model& out, int64_t* n_nodes);
+// ev: null, or the watched fit's arguments (fd_gbdt_fit_eval_*): its outputs are written
 void gbdt_fit_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, int32_t F, const fd_gbdt_params& p,
-                       const fd_gbdt_model& out, int64_t* n_nodes, float* margins);
+                       const fd_gbdt_model& out, int64_t* n_nodes, float* margins, fd_gbdt_eval* ev = nullptr);
+// the limits of fd_gbdt_eval for a fit of n rows -> whether it holds an eval set; host_labels: ev.y is read
+bool gbdt_check_eval(const fd_gbdt_eval& ev, int64_t n, int32_t F, bool host_labels);
+void gbdt_check_metric_labels(const uint8_t* y, int64_t n, int32_t metric);
+double gbdt_metric_ref_host(const float* margin, const uint8_t* y, int64_t n, int32_t metric);
+double gbdt_metric_device(Engine& e, const float* d_margin, const uint8_t* d_y, int64_t n, int32_t metric);
+// ev's X, y, margins and best_margins are device pointers, metric_out a host pointer; h_X may be null
+void gbdt_fit_eval_device(Engine& e, const float* d_X, const float* h_X, const uint8_t* d_y, int64_t n, int32_t ld,
+                          int32_t F, const fd_gbdt_params& p, fd_gbdt_eval& ev, const fd_gbdt_model& out,
+                          int64_t* n_nodes, float* d_margins);
 void launch_gbdt_bin(Engine& e, const float* d_X, int64_t n, int32_t ld, int32_t F, const float* d_cuts,
                      const int32_t* d_offsets, uint8_t* d_bins);
 void launch_gbdt_grad(Engine& e, const float* d_margin, const uint8_t* d_y, int64_t n, int32_t* d_g, int32_t* d_h);

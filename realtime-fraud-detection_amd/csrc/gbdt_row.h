@@ -91,7 +91,8 @@ FD_HD double gbdt_sigmoid(float margin) {
   return e / (1.0 + e);
 }
 
-// v * 2^24 rounded to the nearest integer, ties to even (|v| <= 1): the sum with 1.5 * 2^52 rounds at the units place
+// v * 2^24 rounded to the nearest integer, ties to even (|v| <= 64, the class weight's limit): the sum with
+// 1.5 * 2^52 rounds at the units place
 FD_HD int32_t gbdt_quantise(double v) {
 #pragma clang fp contract(off)
   const double kMagic = 6755399441055744.0;
@@ -107,6 +108,76 @@ FD_HD void gbdt_grad(float margin, int y, int32_t& g, int32_t& h) {
   g = gbdt_quantise(p - (double)y);
   const int32_t hq = gbdt_quantise(p * (1.0 - p));
   h = hq < 1 ? 1 : hq;
+}
+
+// The same pair under a class weight (scale_pos_weight = w, 0 < w <= 64): a positive row's g = quantise(w (p - 1))
+// and h = max(1, quantise(w p (1 - p))), |g| <= 2^30; a negative row keeps gbdt_grad's pair. w == 1 gives gbdt_grad's
+// bits (a product with 1.0 is exact).
+constexpr double kGbdtMaxPosWeight = 64.0;
+FD_HD void gbdt_grad_weighted(float margin, int y, double w, int32_t& g, int32_t& h) {
+#pragma clang fp contract(off)
+  if (!y) {
+    gbdt_grad(margin, y, g, h);
+    return;
+  }
+  const double p = gbdt_sigmoid(margin);
+  g = gbdt_quantise(w * (p - 1.0));
+  const int32_t hq = gbdt_quantise(w * (p * (1.0 - p)));
+  h = hq < 1 ? 1 : hq;
+}
+
+// ------------------------------------------------------------------------------------------------ evaluation
+// The metrics of a held-out set (fd_gbdt_fit_eval_*, fd_gbdt_metric_*): integer statistics and one division each, so
+// their bits depend on neither the launch shape nor the order rows arrive in. Evaluation is never weighted.
+
+// The order key of a margin: a u32 that orders like the float. -0 and +0 share a key (the base margin at base_score
+// 0.5 is -0.0f; an empty node's leaf is -0), +-inf are ordinary values, and every NaN takes the one key above +inf's.
+FD_HD uint32_t gbdt_order_key(float m) {
+  if (!(m == m)) return 0xffffffffu;
+  uint32_t u;
+  memcpy(&u, &m, 4);
+  if ((u & 0x7fffffffu) == 0u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// What is sorted: (key << 1) | label in 33 bits, so that a tie group's negatives stand before its positives
+constexpr int kGbdtSortBits = 33;
+FD_HD uint64_t gbdt_sort_word(float m, int y) { return ((uint64_t)gbdt_order_key(m) << 1) | (uint64_t)(y ? 1 : 0); }
+
+// auc = 2U / (2 P N), 2U = sum over the positive rows of #{negatives with a lower key} + #{negatives with a key not
+// above}: the Mann-Whitney statistic over midranks, doubled. 2U <= 2 P N <= 2^55 at the row limit: both exact in f64.
+FD_HD double gbdt_auc(uint64_t two_u, uint64_t n_pos, uint64_t n_neg) {
+#pragma clang fp contract(off)
+  return (double)two_u / (double)(2ull * n_pos * n_neg);
+}
+// error = #{rows with (margin > 0) != y} / n (a NaN margin predicts 0)
+FD_HD int gbdt_is_error(float m, int y) { return ((m > 0.0f) ? 1 : 0) != (y ? 1 : 0); }
+FD_HD double gbdt_error(uint64_t wrong, uint64_t n) {
+#pragma clang fp contract(off)
+  return (double)wrong / (double)n;
+}
+
+// The stopping rule of XGBoost's EarlyStopping callback, as its documentation states it: round t improves iff its
+// metric is strictly better than the best so far (round 0 always improves); after k consecutive rounds without
+// improvement the fit stops, so that rounds_run = best_round + k + 1. k == 0: never. One state per fit, updated once
+// a round by one thread of the device (gbeval_state_kernel) or by the host reference.
+struct GbdtStopState {
+  double best;
+  int32_t best_round;
+  int32_t since;       // rounds since the best
+  int32_t stop;        // set: no later round runs
+  int32_t rounds_run;
+};
+FD_HD void gbdt_stop_update(GbdtStopState& s, int round, double metric, bool maximise, int k) {
+  s.rounds_run = round + 1;
+  const bool improved = round == 0 || (maximise ? metric > s.best : metric < s.best);
+  if (improved) {
+    s.best = metric;
+    s.best_round = round;
+    s.since = 0;
+    return;
+  }
+  ++s.since;
+  if (k > 0 && s.since >= k) s.stop = 1;
 }
 
 // The samples are functions of (seed, round, index): no generator state. mix() keeps rows and features apart.

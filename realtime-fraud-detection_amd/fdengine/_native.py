@@ -143,6 +143,17 @@ class fd_gbdt_model(C.Structure):
                 ("base_weights", C.c_void_p)]
 
 
+FD_GBDT_METRIC_AUC = 0
+FD_GBDT_METRIC_ERROR = 1
+
+
+class fd_gbdt_eval(C.Structure):
+    _fields_ = [("X", C.c_void_p), ("y", C.c_void_p), ("n", C.c_int64), ("ld", C.c_int32), ("metric", C.c_int32),
+                ("early_stopping_rounds", C.c_int32), ("reserved", C.c_int32), ("scale_pos_weight", C.c_double),
+                ("metric_out", C.c_void_p), ("margins", C.c_void_p), ("best_margins", C.c_void_p),
+                ("rounds_run", C.c_int32), ("best_iteration", C.c_int32)]
+
+
 class fd_iforest_fit_params(C.Structure):
     _fields_ = [("n_estimators", C.c_int32), ("max_samples", C.c_int32), ("max_features", C.c_double),
                 ("contamination", C.c_double), ("seed", C.c_uint64)]
@@ -549,6 +560,15 @@ SIGNATURES = {
                                    C.POINTER(fd_gbdt_model), C.POINTER(_i64), _vp]),
     "fd_gbdt_fit_ref_host": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.POINTER(fd_gbdt_params),
                                        C.POINTER(fd_gbdt_model), C.POINTER(_i64), _vp]),
+    "fd_gbdt_fit_eval_device": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(fd_gbdt_params),
+                                          C.POINTER(fd_gbdt_eval), C.POINTER(fd_gbdt_model), C.POINTER(_i64), _vp]),
+    "fd_gbdt_fit_eval_host": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(fd_gbdt_params),
+                                        C.POINTER(fd_gbdt_eval), C.POINTER(fd_gbdt_model), C.POINTER(_i64), _vp]),
+    "fd_gbdt_fit_eval_ref_host": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.POINTER(fd_gbdt_params),
+                                            C.POINTER(fd_gbdt_eval), C.POINTER(fd_gbdt_model), C.POINTER(_i64), _vp]),
+    "fd_gbdt_metric_host": (C.c_int, [_vp, _vp, _vp, _i64, _i32, C.POINTER(C.c_double)]),
+    "fd_gbdt_metric_ref_host": (C.c_int, [_vp, _vp, _i64, _i32, C.POINTER(C.c_double)]),
+    "fd_gbdt_grad_weighted_ref_host": (C.c_int, [_vp, _vp, _i64, C.c_double, _vp, _vp]),
     "fd_iforest_fit_device": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.POINTER(fd_iforest_fit_params),
                                         C.POINTER(fd_tree_arrays), _vp, C.POINTER(fd_forest_params), C.POINTER(_i64)]),
     "fd_iforest_fit_host": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.POINTER(fd_iforest_fit_params),

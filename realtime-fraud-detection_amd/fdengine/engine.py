@@ -13,7 +13,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _native as N
-from .forest import ForestArrays
+from .forest import ForestArrays, truncate_forest
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -203,14 +203,25 @@ class FraudEngine:
         return phi, idx, val
 
     # ------------------------------------------------------------------ training (histogram GBDT, gbdt.hip)
-    def fit_gbdt(self, X, y, **params) -> ForestArrays:
+    def fit_gbdt(self, X, y, eval_set=None, eval_metric="auc", early_stopping_rounds=None, scale_pos_weight=1.0,
+                 **params) -> ForestArrays:
         """Grow a binary:logistic gbtree forest on the engine (fd_gbdt_fit_*; the declared semantics are DESIGN
         §4.14). X: [n, F <= 64] numpy, or a contiguous f32 torch tensor on this engine's device (then y a uint8 tensor
         there); y: 0 / 1. params: GBDT_DEFAULTS (n_rounds, max_depth, max_bin, eta, reg_lambda, min_child_weight,
         subsample, colsample_bytree, base_score, seed). -> ForestArrays ready for load_forest, cover = sum_hessian,
         meta["sum_hessian" | "loss_changes" | "base_weights"] per node and meta["margins"], the final f32 margins of
-        the rows of X (what predict(..., want_raw=True) reports for them)."""
+        the rows of X (what predict(..., want_raw=True) reports for them).
+
+        eval_set=(X_eval, y_eval) (or a list holding one such pair; the same kind of arrays as X) is evaluated after
+        every round on the device (fd_gbdt_fit_eval_*): eval_metric "auc" or "error", early_stopping_rounds=k stops
+        after k rounds without a strictly better metric, scale_pos_weight weights the positive rows' gradients. Then
+        meta also holds "evals_result" ({"validation_0": {metric: [one value per round run]}}), "best_iteration",
+        "best_score", "rounds_run" and "eval_margins" (the eval rows' margins after the last round run). With early
+        stopping the forest returned is cut to the trees 0 .. best_iteration (what XGBClassifier.predict_proba uses
+        after such a fit, and what any loader of the written file then scores with), and meta["margins"] are that
+        forest's; without, every tree is returned."""
         p = gbdt_params(**params)
+        watched = eval_set is not None or early_stopping_rounds is not None or float(scale_pos_weight) != 1.0
         if type(X).__module__.startswith("torch") and X.is_cuda:
             import torch
             if X.dtype != torch.float32 or X.dim() != 2 or not X.is_contiguous():
@@ -221,15 +232,30 @@ class FraudEngine:
             N.call("fd_gbdt_fit_device", self._h, None, None, n, ld, ld, C.byref(p), None, C.byref(cap), None)
             out = _GbdtOut(p.n_rounds, cap.value)
             margins = torch.zeros(n, dtype=torch.float32, device=X.device)
-            torch.cuda.current_stream(X.device).synchronize()
             nn = C.c_int64()
+            if watched:
+                ev, keep = _gbdt_eval_struct(eval_set, eval_metric, early_stopping_rounds, scale_pos_weight, p, n, ld,
+                                             device=X.device)
+                torch.cuda.current_stream(X.device).synchronize()
+                N.call("fd_gbdt_fit_eval_device", self._h, C.c_void_p(X.data_ptr()), C.c_void_p(y.data_ptr()), n, ld,
+                       ld, C.byref(p), C.byref(ev), C.byref(out.model), C.byref(nn), C.c_void_p(margins.data_ptr()))
+                return _gbdt_eval_forest(out, nn.value, ld, p, ev, keep, margins, eval_metric, early_stopping_rounds)
+            torch.cuda.current_stream(X.device).synchronize()
             N.call("fd_gbdt_fit_device", self._h, C.c_void_p(X.data_ptr()), C.c_void_p(y.data_ptr()), n, ld, ld,
                    C.byref(p), C.byref(out.model), C.byref(nn), C.c_void_p(margins.data_ptr()))
             fa = out.forest(nn.value, ld, p.base_score)
             fa.meta["margins"] = margins
             return fa
         X, y = _gbdt_xy(X, y)
+        if watched:
+            return _gbdt_fit_eval("fd_gbdt_fit_eval_host", (self._h,), X, y, p, eval_set, eval_metric,
+                                  early_stopping_rounds, scale_pos_weight)
         return _gbdt_fit("fd_gbdt_fit_host", (self._h,), X, y, p)
+
+    def gbdt_metric(self, margins, y, metric="auc") -> float:
+        """The eval metric ("auc" or "error") of f32 margins and 0 / 1 labels by the fit's sort and count kernels
+        (fd_gbdt_metric_host)."""
+        return _gbdt_metric("fd_gbdt_metric_host", (self._h,), margins, y, metric)
 
     def gbdt_bin(self, X, cuts, offsets) -> np.ndarray:
         """The u8 bin matrix of X under the cuts, by the bin kernel (fd_gbdt_bin_host)."""
@@ -1227,10 +1253,128 @@ def _gbdt_fit(fn: str, head, X, y, p):
     return fa
 
 
-def gbdt_fit_ref_host(X, y, **params) -> ForestArrays:
-    """Host-only: the single-threaded reference fit (fd_gbdt_fit_ref_host), as FraudEngine.fit_gbdt returns it."""
+GBDT_METRICS = {"auc": N.FD_GBDT_METRIC_AUC, "error": N.FD_GBDT_METRIC_ERROR}
+
+
+def _gbdt_metric_id(metric) -> int:
+    if metric not in GBDT_METRICS:
+        raise ValueError(f"eval_metric must be one of {sorted(GBDT_METRICS)}, not {metric!r}")
+    return GBDT_METRICS[metric]
+
+
+def _gbdt_eval_struct(eval_set, eval_metric, early_stopping_rounds, scale_pos_weight, p, n, F, device=None):
+    """fd_gbdt_eval for a fit of n rows x F columns, with its output arrays (numpy, or torch tensors on `device`)
+    -> (struct, the arrays it points into)."""
+    if isinstance(eval_set, list):
+        if len(eval_set) > 1:
+            raise ValueError("one eval set at most")
+        eval_set = eval_set[0] if eval_set else None
+    k = 0 if early_stopping_rounds is None else int(early_stopping_rounds)
+    if k < 0:
+        raise ValueError("early_stopping_rounds must be >= 0")
+    keep = {"curve": np.zeros(p.n_rounds, np.float64)}
+    ev = N.fd_gbdt_eval()
+    ev.metric = _gbdt_metric_id(eval_metric)
+    ev.early_stopping_rounds = k
+    ev.scale_pos_weight = float(scale_pos_weight)
+    ev.metric_out = keep["curve"].ctypes.data
+    if eval_set is not None:
+        Xe, ye = eval_set
+        if device is not None:
+            import torch
+            if not (type(Xe).__module__.startswith("torch") and Xe.is_cuda and Xe.dtype == torch.float32
+                    and Xe.dim() == 2 and Xe.is_contiguous()):
+                raise ValueError("device input: the eval matrix is a contiguous 2-d float32 tensor there too")
+            ye = ye.to(device=device, dtype=torch.uint8).contiguous()
+            if ye.shape != (Xe.shape[0],):
+                raise ValueError("y: one label per row of X")
+            keep.update(X=Xe, y=ye, eval_margins=torch.zeros(Xe.shape[0], dtype=torch.float32, device=device),
+                        best_margins=torch.zeros(n, dtype=torch.float32, device=device))
+            ptr = {a: keep[a].data_ptr() for a in ("X", "y", "eval_margins", "best_margins")}
+        else:
+            Xe, ye = _gbdt_xy(Xe, ye)
+            keep.update(X=Xe, y=ye, eval_margins=np.zeros(Xe.shape[0], np.float32),
+                        best_margins=np.zeros(n, np.float32))
+            ptr = {a: keep[a].ctypes.data for a in ("X", "y", "eval_margins", "best_margins")}
+        if Xe.shape[1] < F:
+            raise ValueError(f"the eval matrix has {Xe.shape[1]} columns, the fit {F}")
+        ev.n, ev.ld = int(Xe.shape[0]), int(Xe.shape[1])
+        if ev.n:
+            ev.X, ev.y, ev.margins, ev.best_margins = ptr["X"], ptr["y"], ptr["eval_margins"], ptr["best_margins"]
+    return ev, keep
+
+
+def _gbdt_eval_forest(out, n_nodes, F, p, ev, keep, margins, eval_metric, early_stopping_rounds):
+    """The ForestArrays of a watched fit from the C ABI's outputs (every grown tree): cut to the best round's trees
+    when early stopping was asked for."""
+    run = int(ev.rounds_run)
+    out.a["offsets"] = out.a["offsets"][:run + 1]
+    fa = out.forest(n_nodes, F, p.base_score)
+    fa.meta["margins"] = margins
+    fa.meta["rounds_run"] = run
+    if ev.best_iteration < 0:  # no eval set: only the class weight acted
+        return fa
+    curve = keep["curve"][:run].copy()
+    best = int(ev.best_iteration)
+    if early_stopping_rounds is not None and best + 1 < run:
+        fa = truncate_forest(fa, best + 1)
+        fa.meta["margins"] = keep["best_margins"]
+    fa.meta.update(evals_result={"validation_0": {eval_metric: [float(v) for v in curve]}}, best_iteration=best,
+                   best_score=float(curve[best]), eval_margins=keep["eval_margins"])
+    return fa
+
+
+def _gbdt_fit_eval(fn: str, head, X, y, p, eval_set, eval_metric, early_stopping_rounds, scale_pos_weight):
+    """The two calls of fd_gbdt_fit_eval_* on host arrays."""
+    n, ld = X.shape
+    ev, keep = _gbdt_eval_struct(eval_set, eval_metric, early_stopping_rounds, scale_pos_weight, p, n, ld)
+    cap = C.c_int64()
+    N.call(fn, *head, _ptr(X), _ptr(y), n, ld, ld, C.byref(p), None, None, C.byref(cap), None)
+    out = _GbdtOut(p.n_rounds, cap.value)
+    margins = np.zeros(n, np.float32)
+    nn = C.c_int64()
+    N.call(fn, *head, _ptr(X), _ptr(y), n, ld, ld, C.byref(p), C.byref(ev), C.byref(out.model), C.byref(nn),
+           _ptr(margins))
+    return _gbdt_eval_forest(out, nn.value, ld, p, ev, keep, margins, eval_metric, early_stopping_rounds)
+
+
+def gbdt_fit_ref_host(X, y, eval_set=None, eval_metric="auc", early_stopping_rounds=None, scale_pos_weight=1.0,
+                      **params) -> ForestArrays:
+    """Host-only: the single-threaded reference fit (fd_gbdt_fit_ref_host / fd_gbdt_fit_eval_ref_host), as
+    FraudEngine.fit_gbdt returns it."""
     X, y = _gbdt_xy(X, y)
+    if eval_set is not None or early_stopping_rounds is not None or float(scale_pos_weight) != 1.0:
+        return _gbdt_fit_eval("fd_gbdt_fit_eval_ref_host", (), X, y, gbdt_params(**params), eval_set, eval_metric,
+                              early_stopping_rounds, scale_pos_weight)
     return _gbdt_fit("fd_gbdt_fit_ref_host", (), X, y, gbdt_params(**params))
+
+
+def _gbdt_metric(fn: str, head, margins, y, metric) -> float:
+    margins = np.ascontiguousarray(margins, dtype=np.float32).reshape(-1)
+    yy = np.asarray(y).reshape(-1)
+    if yy.shape != margins.shape:
+        raise ValueError("y: one label per margin")
+    if not np.isin(yy, (0, 1)).all():
+        raise ValueError("labels must be 0 or 1")
+    yy = np.ascontiguousarray(yy.astype(np.uint8))
+    v = C.c_double()
+    N.call(fn, *head, _ptr(margins), _ptr(yy), margins.size, _gbdt_metric_id(metric), C.byref(v))
+    return v.value
+
+
+def gbdt_metric_ref_host(margins, y, metric="auc") -> float:
+    """Host-only: the eval metric ("auc" or "error") of f32 margins and 0 / 1 labels (fd_gbdt_metric_ref_host)."""
+    return _gbdt_metric("fd_gbdt_metric_ref_host", (), margins, y, metric)
+
+
+def gbdt_grad_weighted_ref_host(margin, y, scale_pos_weight):
+    """Host-only: the fixed-point (g, h) under a class weight (fd_gbdt_grad_weighted_ref_host)."""
+    margin = np.ascontiguousarray(margin, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.uint8)
+    g, h = np.zeros(margin.size, np.int32), np.zeros(margin.size, np.int32)
+    N.call("fd_gbdt_grad_weighted_ref_host", _ptr(margin), _ptr(y), margin.size, float(scale_pos_weight), _ptr(g),
+           _ptr(h))
+    return g, h
 
 
 def gbdt_cuts_host(X, max_bin: int = 256):

@@ -75,6 +75,20 @@ class ForestArrays:
         return p, t, arrs
 
 
+def truncate_forest(fa: ForestArrays, n_trees: int) -> ForestArrays:
+    """The first n_trees trees of a forest, with the per-node arrays of fit_gbdt's meta cut alike."""
+    end = int(fa.offsets[n_trees])
+    meta = dict(fa.meta, n_trees=n_trees)
+    for k in ("sum_hessian", "loss_changes", "base_weights"):
+        if k in meta:
+            meta[k] = np.asarray(meta[k])[:end].copy()
+    return ForestArrays(kind=fa.kind, num_feature=fa.num_feature, offsets=fa.offsets[:n_trees + 1].copy(),
+                        left=fa.left[:end].copy(), right=fa.right[:end].copy(), feature=fa.feature[:end].copy(),
+                        threshold=fa.threshold[:end].copy(), default_left=fa.default_left[:end].copy(),
+                        leaf_value=fa.leaf_value[:end].copy(), base_score=fa.base_score, meta=meta,
+                        cover=None if fa.cover is None else meta.get("sum_hessian", fa.cover[:end].copy()))
+
+
 def _concat(trees: List[Dict[str, np.ndarray]], kind: int, num_feature: int, **kw) -> ForestArrays:
     sizes = [len(t["left"]) for t in trees]
     offsets = np.zeros(len(trees) + 1, dtype=np.int64)

@@ -4,7 +4,9 @@ the engine.
 
 What differs, on purpose:
 * train_xgboost_model fits with FraudEngine.fit_gbdt (csrc/gbdt.hip) at the reference's parameters (max_depth 6,
-  learning_rate 0.1, subsample 0.8, colsample_bytree 0.8, 100 estimators, random_state as the seed). The fit's
+  learning_rate 0.1, subsample 0.8, colsample_bytree 0.8, 100 estimators, random_state as the seed) and, as the
+  reference does, watches the held-out split (eval_set, AUC per round in evals_result_). early_stopping_rounds and
+  scale_pos_weight are attributes the reference leaves at XGBoost's defaults; so do these. The fit's
   arithmetic is the engine's own declared one: the file it writes is XGBoost 2.0.3 JSON that XGBoost and
   this engine load, but its trees are not the trees XGBoost would have grown.
 * The synthetic frame has the reference's 33 feature columns, label rule and 5 % fraud rate, drawn vectorised from one
@@ -92,6 +94,11 @@ class ModelTrainer:
         self.test_size = 0.2
         self.validation_size = 0.1
         self.random_state = 42
+        # the XGBoost member's fit (FraudEngine.fit_gbdt): stop after this many rounds without a better held-out AUC
+        # (None: never), the positive rows' gradient weight, and after train_xgboost_model the held-out curve
+        self.early_stopping_rounds = None
+        self.scale_pos_weight = 1.0
+        self.evals_result_ = None
         self._engine = engine
         self.logger.info(f"Model trainer initialized with output dir: {output_dir}")
 
@@ -124,7 +131,10 @@ class ModelTrainer:
         self.logger.info("Training XGBoost model...")
         start_time = time.time()
         eng = self.engine
-        fa = eng.fit_gbdt(X_train, y_train, random_state=self.random_state, **XGB_PARAMS)
+        fa = eng.fit_gbdt(X_train, y_train, eval_set=(X_test, y_test), eval_metric="auc",
+                          early_stopping_rounds=self.early_stopping_rounds, scale_pos_weight=self.scale_pos_weight,
+                          random_state=self.random_state, **XGB_PARAMS)
+        self.evals_result_ = fa.meta["evals_result"]
         model_path = os.path.join(self.output_dir, "xgboost", "fraud_classifier.json")
         os.makedirs(os.path.dirname(model_path), exist_ok=True)
         with open(model_path, "w") as f:

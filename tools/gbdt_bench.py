@@ -15,6 +15,18 @@ scikit-learn's HistGradientBoostingClassifier(max_iter, max_depth, learning_rate
 early_stopping=False) on the same data with the process's thread limit (OMP_NUM_THREADS, 16 where this is run): the
 only histogram GBDT on the machine. It is another algorithm's wall time, not a parity check.
 
+The watched fit (eval_set, early stopping; DESIGN §4.14 "Evaluation") has four parts of its own, written to
+profiles/gbdt_eval/gbdt_eval_bench.jsonl:
+
+ unchanged   a fit without the new arguments at the trainer and the serving shape, timed by child processes that
+             alternate between another build of the tree (PARENT_TREE, default ab_prev/: a checkout of the parent
+             commit, built) and this one: what the new code costs a caller who does not use it;
+ eval_cost   the same two fits with a 20 % eval set (2,000 / 200,000 rows), AUC and error: the overhead per round;
+ caller_loop the trainer shape's curve on the device against what a caller did before: per round truncate, load_forest,
+             predict, roc_auc_midrank on the host;
+ early_stop  both shapes with early_stopping_rounds=10: rounds run, wall time and held-out AUC of the cut forest
+             against the full 100 rounds.
+
 Prints one JSON line per part and appends it to profiles/gbdt/gbdt_bench.jsonl (OUT overrides the path).
 Arguments: the parts to run (default: trainer serving headline)."""
 import json
@@ -26,6 +38,9 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parent.parent
 sys.path[:0] = [str(REPO), str(REPO / "realtime-fraud-detection_amd")]
 import numpy as np
+
+if len(sys.argv) > 2 and sys.argv[1] == "_plain_child":  # a child of the "unchanged" part: the tree it is told to use
+    sys.path[:0] = [sys.argv[2], sys.argv[2] + "/realtime-fraud-detection_amd"]
 
 import fdengine
 from fdengine import synth
@@ -141,9 +156,129 @@ def headline(eng):
           "train_auc": roc_auc_midrank(y, fa.meta["margins"])})
 
 
-def main():
-    parts = sys.argv[1:] or ["trainer", "serving", "headline"]
+EVAL_OUT = REPO / "profiles" / "gbdt_eval" / "gbdt_eval_bench.jsonl"
+TRAINER_PARAMS = dict(n_rounds=100, max_depth=6, eta=0.1, subsample=0.8, colsample_bytree=0.8, seed=42)
+SERVING_PARAMS = dict(n_rounds=100, max_depth=8, eta=0.1, seed=42)
+
+
+def trainer_data():
+    tr = ModelTrainer(output_dir=os.environ.get("TMPDIR", "/tmp") + "/gbdt_bench_models")
+    Xa, Xb, ya, yb = tr.prepare_training_data()
+    return Xa.astype(np.float32), ya.astype(np.uint8), Xb.astype(np.float32), yb.astype(np.uint8)
+
+
+def serving_data(n_eval):
+    n = int(os.environ.get("SERVING_ROWS", 1000000))
+    X = synth.feature_matrix(n + n_eval, 64, seed=2000)
+    y = fraud_label(X, 2001)
+    return X[:n], y[:n], X[n:], y[n:]
+
+
+def plain_child(shape, regions):
+    """Timed fits without the new arguments, in this process's tree -> one JSON line on stdout."""
+    X, y, _, _ = trainer_data() if shape == "trainer" else serving_data(1000)
+    params = TRAINER_PARAMS if shape == "trainer" else SERVING_PARAMS
     eng = fdengine.FraudEngine(0)
+    secs, _ = timed_fits(lambda: eng.fit_gbdt(X, y, **params), 1, regions)
+    eng.close()
+    print(json.dumps({"fit_s": secs}), flush=True)
+
+
+def unchanged():
+    import subprocess
+    parent = os.environ.get("PARENT_TREE", str(REPO / "ab_prev"))
+    for shape, regions, turns in (("trainer", 7, 3), ("serving", 2, 2)):
+        runs = {"parent": [], "this": []}
+        for _ in range(turns):  # parent, this, parent, this ...: drift of the machine falls on both alike
+            for who, tree in (("parent", parent), ("this", str(REPO))):
+                r = subprocess.run([sys.executable, __file__, "_plain_child", tree, shape, str(regions)],
+                                   capture_output=True, text=True, timeout=600, check=True)
+                runs[who].append(json.loads(r.stdout.strip().splitlines()[-1])["fit_s"])
+        med = {w: [float(np.median(t)) for t in v] for w, v in runs.items()}
+        emit({"part": "unchanged", "shape": shape, "fits_per_turn": regions, "parent_fit_s": runs["parent"],
+              "this_fit_s": runs["this"], "parent_turn_medians_s": med["parent"], "this_turn_medians_s": med["this"],
+              "parent_median_s": float(np.median(sum(runs["parent"], []))),
+              "this_median_s": float(np.median(sum(runs["this"], []))),
+              "parent_spread_of_turn_medians_s": max(med["parent"]) - min(med["parent"]),
+              "parent_spread_of_fits_s": max(sum(runs["parent"], [])) - min(sum(runs["parent"], []))})
+
+
+def eval_cost(eng, shape, X, y, Xe, ye, params, warmup, regions):
+    line = {"part": "eval_cost", "shape": shape, "rows": len(X), "eval_rows": len(Xe), "rounds": params["n_rounds"]}
+    plain, _ = timed_fits(lambda: eng.fit_gbdt(X, y, **params), warmup, regions)
+    line.update(plain_fit_s=plain, plain_round_ms=float(np.median(plain)) / params["n_rounds"] * 1e3)
+    for metric in ("auc", "error"):
+        secs, fa = timed_fits(lambda: eng.fit_gbdt(X, y, eval_set=(Xe, ye), eval_metric=metric, **params), warmup,
+                              regions)
+        line.update({f"{metric}_fit_s": secs, f"{metric}_overhead_per_round_ms":
+                     (float(np.median(secs)) - float(np.median(plain))) / params["n_rounds"] * 1e3,
+                     f"{metric}_last": fa.meta["evals_result"]["validation_0"][metric][-1]})
+    emit(line)
+    return fa
+
+
+def caller_loop(eng, X, y, Xe, ye, params):
+    from fdengine import truncate_forest
+    dev, _ = timed_fits(lambda: eng.fit_gbdt(X, y, eval_set=(Xe, ye), **params), 1, 5)
+    fa = eng.fit_gbdt(X, y, **params)
+
+    def loop():
+        fit = eng.fit_gbdt(X, y, **params)
+        curve = []
+        for t in range(fit.n_trees):
+            eng.load_forest(0, truncate_forest(fit, t + 1))
+            curve.append(roc_auc_midrank(ye, eng.predict(0, Xe, want_raw=True)[1]))
+            eng.unload_forest(0)
+        return curve
+
+    host, curve = timed_fits(loop, 0, 2)
+    watched = eng.fit_gbdt(X, y, eval_set=(Xe, ye), **params)
+    emit({"part": "caller_loop", "rows": len(X), "eval_rows": len(Xe), "rounds": params["n_rounds"],
+          "device_curve_fit_s": dev, "device_curve_fit_s_median": float(np.median(dev)),
+          "fit_then_host_loop_s": host, "fit_then_host_loop_s_median": float(np.median(host)),
+          "curves_equal": curve == watched.meta["evals_result"]["validation_0"]["auc"], "nodes": int(len(fa.left))})
+
+
+def early_stop(eng, shape, X, y, Xe, ye, params, k):
+    eng.fit_gbdt(X, y, eval_set=(Xe, ye), early_stopping_rounds=k, **params)  # warm-up: the buffers exist
+    t0 = time.perf_counter()
+    full = eng.fit_gbdt(X, y, eval_set=(Xe, ye), **params)
+    t_full = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    cut = eng.fit_gbdt(X, y, eval_set=(Xe, ye), early_stopping_rounds=k, **params)
+    t_cut = time.perf_counter() - t0
+    curve = full.meta["evals_result"]["validation_0"]["auc"]
+    emit({"part": "early_stop", "shape": shape, "rows": len(X), "eval_rows": len(Xe), "rounds": params["n_rounds"],
+          "early_stopping_rounds": k, "rounds_run": cut.meta["rounds_run"], "best_iteration": cut.meta["best_iteration"],
+          "full_fit_s": t_full, "stopped_fit_s": t_cut, "trees_returned": cut.n_trees,
+          "eval_auc_cut_forest": cut.meta["best_score"], "eval_auc_full_forest": curve[-1],
+          "eval_auc_curve_every_10": curve[9::10]})
+
+
+def main():
+    global OUT
+    if len(sys.argv) > 2 and sys.argv[1] == "_plain_child":
+        return plain_child(sys.argv[3], int(sys.argv[4]))
+    parts = sys.argv[1:] or ["trainer", "serving", "headline"]
+    if {"unchanged", "eval_cost", "caller_loop", "early_stop"} & set(parts) and "OUT" not in os.environ:
+        OUT = EVAL_OUT
+    if "unchanged" in parts:  # (before this process opens the device: one process at a time holds it)
+        unchanged()
+    eng = fdengine.FraudEngine(0)
+    if {"eval_cost", "caller_loop", "early_stop"} & set(parts):
+        Xa, ya, Xb, yb = trainer_data()
+        if "eval_cost" in parts:
+            eval_cost(eng, "trainer", Xa, ya, Xb, yb, TRAINER_PARAMS, 2, 7)
+        if "caller_loop" in parts:
+            caller_loop(eng, Xa, ya, Xb, yb, TRAINER_PARAMS)
+        if "early_stop" in parts:
+            early_stop(eng, "trainer", Xa, ya, Xb, yb, TRAINER_PARAMS, 10)
+    if {"eval_cost", "early_stop"} & set(parts):
+        X, y, Xe, ye = serving_data(200000)
+        if "eval_cost" in parts:
+            eval_cost(eng, "serving", X, y, Xe, ye, SERVING_PARAMS, 1, 2)
+        if "early_stop" in parts:
+            early_stop(eng, "serving", X, y, Xe, ye, SERVING_PARAMS, 10)
     if "trainer" in parts:
         tr = ModelTrainer(output_dir=os.environ.get("TMPDIR", "/tmp") + "/gbdt_bench_models", engine=eng)
         Xa, Xb, ya, yb = tr.prepare_training_data()
