@@ -767,6 +767,91 @@ int fd_pack_mlp_host(const fd_mlp_params* params, void* blob, int64_t cap, int64
    ml/models/ensemble_predictor.py's per-model predict over the same features). */
 #define FD_SLOT_MLP 65
 
+/* ---------------------------------------------------------------- training: the PyTorch MLP member (ModelTrainer) */
+/* Fits the MLP that fd_load_mlp serves (the registry's graph_neural entry; the reference's trainer promises such a
+   trainer and holds none). The semantics are the engine's own and declared (csrc/mlp_fit_row.h):
+   minibatch training of n_layers nn.Linear layers, ReLU and inverted dropout (scale 1 / (1 - dropout)) after every
+   layer but the last, loss = cross_entropy(logits, y, weight = [1, pos_weight]) with mean reduction (the weighted sum
+   over the batch's rows divided by the sum of their weights), optimiser torch.optim.Adam (bias correction, weight_decay
+   as L2 added to the gradient) or torch.optim.SGD (momentum, weight_decay, no Nesterov, no dampening), state in f32.
+   key = fmix64(seed + 0x9e3779b97f4a7c15). Epoch e's row order is the stable ascending sort of the rows r by
+   fmix64(key ^ (e << 32 | r)); step j of an epoch takes rows [j batch_size, min(n, (j + 1) batch_size)) of that order
+   (the last batch is the short remainder, its mean over its own rows). Global step s = e ceil(n / batch_size) + j.
+   Unit u of hidden layer i of the batch's row b (its position in the batch) is kept at step s iff
+   fmix64(fmix64(~key ^ (s << 3 | i)) ^ (b << 6 | u)) >> 32 >= floor(dropout 2^32).
+   A batch's gradient is the sum of per-chunk partials, a chunk being one 16-row tile of the batch (rows 16 c .. 16 c +
+   15 of the batch): each partial is an f32 sum over the chunk's rows, the partials are added in ascending chunk order
+   in an f64 accumulator, divided there by the batch's weight sum and rounded to f32 once. No float atomics,
+   and the bits of a fit depend on neither the grid nor the option "mlp_fit_chunks_per_wg". Each step's loss is reduced
+   the same way and accumulated per epoch in f64; loss_curve[e] is the mean of epoch e's batch losses. The optimiser's
+   scalars (1 - beta1, 1 - beta2, lr / (1 - beta1^t), sqrt(1 - beta2^t)) are formed in f64 and rounded to f32, as
+   torch hands them to its f32 tensor operations.
+   Limits as fd_pack_mlp_host's (FD_ERR_UNSUPPORTED: n_layers outside 2..8, a width outside 1..64, outputs != 2);
+   FD_ERR_INVALID_ARG: epochs < 1, batch_size < 1, n < 1, ld < dims[0], dropout outside [0, 1), pos_weight or a
+   constant of the optimiser not finite or out of its range, a null initial weight; FD_ERR_UNSUPPORTED:
+   batch_size > 65536, n > 2^31 - 1, epochs * n > 2^29 (the index arrays of every epoch are built once). The initial
+   weights are the caller's (fdengine.mlp.random_weights gives nn.Linear's default ranges; a fitted model warm-starts). */
+#define FD_MLP_OPT_ADAM 0
+#define FD_MLP_OPT_SGD 1
+typedef struct {
+  int32_t n_layers;               /* 2..8 */
+  int32_t dims[9];                /* as fd_mlp_params */
+  int32_t epochs;                 /* >= 1 */
+  int32_t batch_size;             /* 1..65536 */
+  int32_t optimizer;              /* FD_MLP_OPT_* */
+  int32_t reserved;
+  double lr, beta1, beta2, eps;   /* Adam: lr > 0, betas in [0, 1), eps > 0; SGD reads lr */
+  double momentum;                /* SGD, [0, 1) */
+  double weight_decay;            /* >= 0 */
+  double dropout;                 /* [0, 1) */
+  double pos_weight;              /* > 0: the weight of a row of class 1 */
+  uint64_t seed;
+  const float* init_weight[8];    /* layer i: [dims[i+1] x dims[i]] row-major */
+  const float* init_bias[8];      /* layer i: [dims[i+1]] or NULL (zeros) */
+} fd_mlp_fit_params;
+/* Host arrays the fit (or fd_mlp_grad_*: the gradients) is written to: weight[i] [dims[i+1] x dims[i]], bias[i]
+   [dims[i+1]], loss_curve [epochs] (fd_mlp_grad_*: one value, the batch's loss; may be NULL), steps (optimiser steps
+   run; fd_mlp_grad_*: 0). */
+typedef struct {
+  float* weight[8];
+  float* bias[8];
+  double* loss_curve;
+  int64_t steps;
+} fd_mlp_fit_out;
+/* The whole fit. X n x ld f32 (columns >= dims[0] are never read), y n bytes of 0 / 1. _device: d_X and d_y are device
+   pointers; _host stages them once. The fit is a stream of two launches per step (mlp_fit_step_kernel: forward,
+   backward and the chunk partials on v_mfma_f32_16x16x4_f32; mlp_fit_update_kernel: the ordered sum, the optimiser,
+   the operand blobs rewritten in place) with no copy or wait between steps; weights and loss_curve come back once.
+   _host and _ref_host refuse (FD_ERR_INVALID_ARG) a label outside {0, 1} and a non-finite value in X; _device trusts the
+   caller (any nonzero label counts as 1). _ref_host: the same rules in single-threaded plain C++, no device; it sums
+   in its own order, so it agrees with the device to rounding, not bit for bit. Counters "mlp_fit_steps",
+   "mlp_fit_launches" (2 per step; fd_mlp_grad_*: 2 per call). */
+int fd_mlp_fit_device(fd_engine* eng, const float* d_X, const uint8_t* d_y, int64_t n, int32_t ld,
+                      const fd_mlp_fit_params* params, fd_mlp_fit_out* out);
+int fd_mlp_fit_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n, int32_t ld,
+                    const fd_mlp_fit_params* params, fd_mlp_fit_out* out);
+int fd_mlp_fit_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, const fd_mlp_fit_params* params,
+                        fd_mlp_fit_out* out);
+/* Loss and every gradient of ONE batch (the n rows of X in their order, 1 <= n <= 65536) at the weights params->init_*:
+   what a step computes before its optimiser. masks: NULL (every unit kept), or (n_layers - 1) x n x 64 bytes, nonzero =
+   kept, [layer][row][unit]; a kept unit is scaled by 1 / (1 - params->dropout). Of params the shape, dropout, pos_weight
+   and the weights are read. _device: d_X, d_y, d_masks are device pointers, out host arrays. */
+int fd_mlp_grad_device(fd_engine* eng, const float* d_X, const uint8_t* d_y, int64_t n, int32_t ld,
+                       const fd_mlp_fit_params* params, const uint8_t* d_masks, fd_mlp_fit_out* out);
+int fd_mlp_grad_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n, int32_t ld,
+                     const fd_mlp_fit_params* params, const uint8_t* masks, fd_mlp_fit_out* out);
+int fd_mlp_grad_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, const fd_mlp_fit_params* params,
+                         const uint8_t* masks, fd_mlp_fit_out* out);
+/* What a fit of n rows trains on: order (n entries, may be NULL) receives epoch `epoch`'s row order, masks (may be
+   NULL; (n_layers - 1) x rows x 64 bytes, the layout fd_mlp_grad_* reads) the dropout masks of global step `step`,
+   *rows that step's batch rows. Of params the shape, epochs, batch_size, dropout and seed are read. _host: plain C++.
+   _device: the order as the fit uploads it, read back from the device; the masks by a kernel of the step kernel's
+   hash. */
+int fd_mlp_fit_batch_host(int64_t n, const fd_mlp_fit_params* params, int32_t epoch, int64_t step, int32_t* order,
+                          uint8_t* masks, int32_t* rows);
+int fd_mlp_fit_batch_device(fd_engine* eng, int64_t n, const fd_mlp_fit_params* params, int32_t epoch, int64_t step,
+                            int32_t* order, uint8_t* masks, int32_t* rows);
+
 /* ---------------------------------------------------------------- transaction-network features (graph detector) */
 /* Replaces GraphFraudDetector._add_transaction_to_history + _calculate_network_features
    (ml/models/graph_neural_network.py:228-242, 338-392): a rolling log of recent transactions, one global arrival
@@ -1380,6 +1465,8 @@ int fd_engine_set_timing(fd_engine* eng, int enable);
      "lstm_rows": LSTM tile, 0 auto (4 transactions below 4096, else 16), 4 or 16
      "mlp_form": the MLP head's kernel for the reference shape (3 layers, padded widths 64): 0 (default) weights in
      registers, 1 the LDS form every other shape takes
+     "mlp_fit_chunks_per_wg": the MLP fit's step kernel, chunks (16-row tiles of the batch) a workgroup takes in turn:
+       0 (default) one each, up to 2^30 (one workgroup for the whole batch); every value gives the same bits
      "mlp_wgs_per_cu": the MLP head's persistent grid, workgroups per CU: 0 (default) two where they fit, else 1..8
      (capped by what fits)
      "timing_every": N >= 1, fd_engine_set_timing records HIP events on one launch in N of each timing kind
@@ -1436,6 +1523,8 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value);
    nor "gbdt_eval_launches"),
    "iforest_fit_trees" (IsolationForest trees grown on the device by fd_iforest_fit_device / _host /
    _grow_tree_host), "iforest_fit_nodes_split" (split nodes of those trees),
+   "mlp_fit_steps" (optimiser steps of the MLP fits), "mlp_fit_launches" (launches of the fit's step and update
+   kernels: 2 per step),
    "mlp_launches" (launches of the MLP head's kernel), "graph_steps" (fd_graph_step_* calls with n > 0),
    "text_calls" (fd_text_features_device / _host calls with n > 0), "text_nonascii_rows" (rows those calls flagged
    FD_TEXT_NONASCII; reading it waits for the engine stream),

@@ -263,6 +263,11 @@ int fd_engine_get_counter(fd_engine* eng, const char* key, int64_t* value) {
     *value = (int64_t)e.iforest.trees;
   } else if (k == "iforest_fit_nodes_split") {  // split nodes of those trees
     *value = (int64_t)e.iforest.nodes_split;
+  } else if (k == "mlp_fit_steps") {  // optimiser steps of the MLP fits (fd_mlp_fit_device / _host)
+    *value = (int64_t)e.mlp_fit.steps;
+  } else if (k == "mlp_fit_launches") {  // launches of mlp_fit_step_kernel and mlp_fit_update_kernel: 2 per step, 2 per
+    // fd_mlp_grad_device / _host call
+    *value = (int64_t)e.mlp_fit.launches;
   } else if (k == "mlp_launches") {  // launches of the MLP head's kernel (fd_mlp_predict_*, FD_SLOT_MLP models)
     *value = (int64_t)e.mlp_total;
   } else if (k == "graph_steps") {  // fd_graph_step_* calls that appended transactions
@@ -458,6 +463,11 @@ int fd_engine_set_option(fd_engine* eng, const char* key, int64_t value) {
   } else if (k == "mlp_wgs_per_cu") {  // MLP head's persistent grid: workgroups per CU, 0 auto (2 where they fit)
     FD_REQUIRE(value >= 0 && value <= 8, FD_ERR_INVALID_ARG, "mlp_wgs_per_cu must be in 0..8");
     e.mlp_wgs_per_cu = (int)value;
+  } else if (k == "mlp_fit_chunks_per_wg") {  // mlp_fit.hip: chunks (16-row tiles of the batch) a workgroup of the step
+    // kernel takes in turn (the grid follows), 0 (default) one each; a chunk's partial depends on the batch alone, so
+    // every value gives the same bits
+    FD_REQUIRE(value >= 0 && value <= (1 << 30), FD_ERR_INVALID_ARG, "mlp_fit_chunks_per_wg must be in 0..2^30");
+    e.mlp_fit.chunks_per_wg = (int)value;
   } else if (k == "ingest_stop_after") {  // diagnostics: 0 full; 1 stage; 2 + structure; 3 + members
     FD_REQUIRE(value >= 0 && value <= 3, FD_ERR_INVALID_ARG, "ingest_stop_after must be in 0..3");
     e.ingest.stop_after = (int)value;
@@ -1377,6 +1387,110 @@ int fd_iforest_fit_grow_tree_host(fd_engine* eng, const float* X, int64_t n, int
   st.upload();
   fd::iforest_fit_grow_tree_device(e, dX, n, ld, F, rows, m, feature_mask, *params, tree, *out, n_node_samples,
                                    n_nodes);
+  FD_API_END
+}
+
+// ---------------------------------------------------------------- training: the PyTorch MLP member (mlp_fit.hip)
+
+int fd_mlp_fit_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, const fd_mlp_fit_params* params,
+                        fd_mlp_fit_out* out) {
+  FD_API_BEGIN
+  FD_REQUIRE(params && out, FD_ERR_INVALID_ARG, "mlp_fit: null params / out");
+  fd::mlp_fit_ref_host(X, y, n, ld, *params, *out);
+  FD_API_END
+}
+
+int fd_mlp_fit_device(fd_engine* eng, const float* d_X, const uint8_t* d_y, int64_t n, int32_t ld,
+                      const fd_mlp_fit_params* params, fd_mlp_fit_out* out) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params && out, FD_ERR_INVALID_ARG, "mlp_fit: null params / out");
+  fd::mlp_fit_device(e, d_X, d_y, n, ld, *params, *out);
+  FD_API_END
+}
+
+int fd_mlp_fit_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n, int32_t ld,
+                    const fd_mlp_fit_params* params, fd_mlp_fit_out* out) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params && out, FD_ERR_INVALID_ARG, "mlp_fit: null params / out");
+  fd::mlp_fit_check(*params, n, ld, true);
+  fd::mlp_fit_check_inputs(X, y, n, ld, *params);
+  Stage st(e);
+  const float* dX;
+  const uint8_t* dy;
+  st.in(dX, X, (size_t)n * ld);
+  st.in(dy, y, (size_t)n);
+  st.upload();
+  fd::mlp_fit_device(e, dX, dy, n, ld, *params, *out);
+  FD_API_END
+}
+
+int fd_mlp_grad_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, const fd_mlp_fit_params* params,
+                         const uint8_t* masks, fd_mlp_fit_out* out) {
+  FD_API_BEGIN
+  FD_REQUIRE(params && out, FD_ERR_INVALID_ARG, "mlp_grad: null params / out");
+  fd::mlp_grad_ref_host(X, y, n, ld, *params, masks, *out);
+  FD_API_END
+}
+
+int fd_mlp_grad_device(fd_engine* eng, const float* d_X, const uint8_t* d_y, int64_t n, int32_t ld,
+                       const fd_mlp_fit_params* params, const uint8_t* d_masks, fd_mlp_fit_out* out) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params && out, FD_ERR_INVALID_ARG, "mlp_grad: null params / out");
+  fd::mlp_grad_device(e, d_X, d_y, n, ld, *params, d_masks, *out);
+  FD_API_END
+}
+
+int fd_mlp_grad_host(fd_engine* eng, const float* X, const uint8_t* y, int64_t n, int32_t ld,
+                     const fd_mlp_fit_params* params, const uint8_t* masks, fd_mlp_fit_out* out) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  FD_REQUIRE(params && out, FD_ERR_INVALID_ARG, "mlp_grad: null params / out");
+  fd::mlp_fit_check(*params, n, ld, false);
+  fd::mlp_fit_check_inputs(X, y, n, ld, *params);
+  Stage st(e);
+  const float* dX;
+  const uint8_t* dy;
+  const uint8_t* dm;
+  st.in(dX, X, (size_t)n * ld);
+  st.in(dy, y, (size_t)n);
+  st.in(dm, masks, (size_t)(params->n_layers - 1) * n * 64);
+  st.upload();
+  fd::mlp_grad_device(e, dX, dy, n, ld, *params, dm, *out);
+  FD_API_END
+}
+
+// what the two batch seams check before an order or a mask is computed (no weights are read)
+static void mlp_batch_check(int64_t n, const fd_mlp_fit_params* params) {
+  FD_REQUIRE(params, FD_ERR_INVALID_ARG, "mlp_fit: null params");
+  FD_REQUIRE(params->n_layers >= 2 && params->n_layers <= 8, FD_ERR_UNSUPPORTED, "MLP n_layers must be in [2, 8]");
+  FD_REQUIRE(n >= 1 && n <= 2147483647ll, FD_ERR_INVALID_ARG, "mlp_fit: n must be in 1..2^31 - 1");
+  FD_REQUIRE(params->epochs >= 1 && params->batch_size >= 1 && params->batch_size <= 65536, FD_ERR_INVALID_ARG,
+             "mlp_fit: epochs must be at least 1 and batch_size in 1..65536");
+  FD_REQUIRE(params->dropout >= 0.0 && params->dropout < 1.0, FD_ERR_INVALID_ARG, "mlp_fit: dropout must be in [0, 1)");
+}
+
+int fd_mlp_fit_batch_host(int64_t n, const fd_mlp_fit_params* params, int32_t epoch, int64_t step, int32_t* order,
+                          uint8_t* masks, int32_t* rows) {
+  FD_API_BEGIN
+  mlp_batch_check(n, params);
+  fd::mlp_fit_batch_ref_host(n, *params, epoch, step, order, masks, rows);
+  FD_API_END
+}
+
+int fd_mlp_fit_batch_device(fd_engine* eng, int64_t n, const fd_mlp_fit_params* params, int32_t epoch, int64_t step,
+                            int32_t* order, uint8_t* masks, int32_t* rows) {
+  FD_API_BEGIN
+  FD_ENGINE_LOCK(eng);
+  Engine& e = E(eng);
+  mlp_batch_check(n, params);
+  fd::mlp_fit_batch_device(e, n, *params, epoch, step, order, masks, rows);
   FD_API_END
 }
 

@@ -284,6 +284,16 @@ struct IForestFitScratch {
   unsigned long long trees = 0, nodes_split = 0;
 };
 
+// mlp_fit.hip: device buffers of a fit (they grow and stay) — the shape words, the forward and transposed operand
+// blobs, the flat master parameters and the optimiser's two moments, the chunk partials with their loss / weight sums,
+// every epoch's index array, the epochs' f64 loss sums, a step's masks (fd_mlp_fit_batch_device) — the option
+// "mlp_fit_chunks_per_wg" (0: a chunk per workgroup) and the counters "mlp_fit_steps" / "mlp_fit_launches"
+struct MlpFitScratch {
+  DeviceBuffer shape, fwd, bwd, w, m, v, partial, lossw, idx, loss, masks;
+  int chunks_per_wg = 0;
+  unsigned long long steps = 0, launches = 0;
+};
+
 // The fused ensemble kernel's joint repack of one XGBoost and/or one IsolationForest (ensemble_plan.hip build_plan):
 // both padded to one depth D, node words rewritten against the MERGED per-feature threshold tables, so one bin
 // tile serves both forests; chunks of CH[k] node-only trees, leaf values [tree][2^D] per forest.
@@ -908,6 +918,7 @@ struct Engine {
   DeviceBuffer shap_partial;                  // shap.hip: per-chunk sums of one row batch, [chunk][column][row]
   GbdtScratch gbdt;                           // gbdt.hip: the fit's device buffers and counters
   IForestFitScratch iforest;                  // iforest_fit.hip: the fit's device buffers and counters
+  MlpFitScratch mlp_fit;                      // mlp_fit.hip: the fit's device buffers, option and counters
   unsigned long long ens_single_total = 0;    // counter "ensemble_single_launches": fd_forest_predict batches run by
                                               // the fused kernel over one forest (config 2's timed kernel)
   int small_streams = 0;  // score_matrix, latency batches: side streams for the LSTM / other forests (score.hip)
@@ -1253,6 +1264,23 @@ void iforest_fit_grow_tree_ref_host(const float* X, int64_t n, int32_t ld, int32
 void iforest_fit_grow_tree_device(Engine& e, const float* d_X, int64_t n, int32_t ld, int32_t F, const int32_t* rows,
                                   int32_t m, uint64_t feature_mask, const fd_iforest_fit_params& p, int32_t tree,
                                   fd_tree_arrays& out, double* n_node_samples, int64_t* n_nodes);
+// mlp_fit.hip: the MLP member's fit (include/fdengine.h "training: the PyTorch MLP member"; the counter-based rules
+// are mlp_fit_row.h). Host pointers unless named d_*; the outputs are host arrays. fit: the whole fit's limits (else a
+// gradient call's).
+void mlp_fit_check(const fd_mlp_fit_params& p, int64_t n, int32_t ld, bool fit);
+void mlp_fit_check_inputs(const float* X, const uint8_t* y, int64_t n, int32_t ld, const fd_mlp_fit_params& p);
+void mlp_fit_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, const fd_mlp_fit_params& p,
+                      fd_mlp_fit_out& out);
+void mlp_fit_device(Engine& e, const float* d_X, const uint8_t* d_y, int64_t n, int32_t ld,
+                    const fd_mlp_fit_params& p, fd_mlp_fit_out& out);
+void mlp_grad_ref_host(const float* X, const uint8_t* y, int64_t n, int32_t ld, const fd_mlp_fit_params& p,
+                       const uint8_t* masks, fd_mlp_fit_out& out);
+void mlp_grad_device(Engine& e, const float* d_X, const uint8_t* d_y, int64_t n, int32_t ld,
+                     const fd_mlp_fit_params& p, const uint8_t* d_masks, fd_mlp_fit_out& out);
+void mlp_fit_batch_ref_host(int64_t n, const fd_mlp_fit_params& p, int32_t epoch, int64_t step, int32_t* order,
+                            uint8_t* masks, int32_t* rows);
+void mlp_fit_batch_device(Engine& e, int64_t n, const fd_mlp_fit_params& p, int32_t epoch, int64_t step,
+                          int32_t* order, uint8_t* masks, int32_t* rows);
 // shap.hip: path-dependent TreeSHAP (include/fdengine.h "forest attribution")
 struct ShapTable {
   std::vector<fd_shap_path> paths;

@@ -205,6 +205,23 @@ class fd_mlp_params(C.Structure):
                 ("bias", C.c_void_p * 8)]
 
 
+FD_MLP_OPT_ADAM = 0
+FD_MLP_OPT_SGD = 1
+
+
+class fd_mlp_fit_params(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("dims", C.c_int32 * 9), ("epochs", C.c_int32), ("batch_size", C.c_int32),
+                ("optimizer", C.c_int32), ("reserved", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_double), ("momentum", C.c_double), ("weight_decay", C.c_double),
+                ("dropout", C.c_double), ("pos_weight", C.c_double), ("seed", C.c_uint64),
+                ("init_weight", C.c_void_p * 8), ("init_bias", C.c_void_p * 8)]
+
+
+class fd_mlp_fit_out(C.Structure):
+    _fields_ = [("weight", C.c_void_p * 8), ("bias", C.c_void_p * 8), ("loss_curve", C.c_void_p),
+                ("steps", C.c_int64)]
+
+
 class fd_graph_params(C.Structure):
     _fields_ = [("max_history", C.c_int32)]
 
@@ -585,6 +602,19 @@ SIGNATURES = {
     "fd_iforest_fit_grow_tree_ref_host": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, C.c_uint64,
                                                     C.POINTER(fd_iforest_fit_params), _i32,
                                                     C.POINTER(fd_tree_arrays), _vp, C.POINTER(_i64)]),
+    "fd_mlp_fit_device": (C.c_int, [_vp, _vp, _vp, _i64, _i32, C.POINTER(fd_mlp_fit_params),
+                                    C.POINTER(fd_mlp_fit_out)]),
+    "fd_mlp_fit_host": (C.c_int, [_vp, _vp, _vp, _i64, _i32, C.POINTER(fd_mlp_fit_params), C.POINTER(fd_mlp_fit_out)]),
+    "fd_mlp_fit_ref_host": (C.c_int, [_vp, _vp, _i64, _i32, C.POINTER(fd_mlp_fit_params), C.POINTER(fd_mlp_fit_out)]),
+    "fd_mlp_grad_device": (C.c_int, [_vp, _vp, _vp, _i64, _i32, C.POINTER(fd_mlp_fit_params), _vp,
+                                     C.POINTER(fd_mlp_fit_out)]),
+    "fd_mlp_grad_host": (C.c_int, [_vp, _vp, _vp, _i64, _i32, C.POINTER(fd_mlp_fit_params), _vp,
+                                   C.POINTER(fd_mlp_fit_out)]),
+    "fd_mlp_grad_ref_host": (C.c_int, [_vp, _vp, _i64, _i32, C.POINTER(fd_mlp_fit_params), _vp,
+                                       C.POINTER(fd_mlp_fit_out)]),
+    "fd_mlp_fit_batch_host": (C.c_int, [_i64, C.POINTER(fd_mlp_fit_params), _i32, _i64, _vp, _vp, C.POINTER(_i32)]),
+    "fd_mlp_fit_batch_device": (C.c_int, [_vp, _i64, C.POINTER(fd_mlp_fit_params), _i32, _i64, _vp, _vp,
+                                          C.POINTER(_i32)]),
 }
 
 

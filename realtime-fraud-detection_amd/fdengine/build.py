@@ -19,7 +19,7 @@ CSRC = PKG_ROOT / "csrc"
 LIB_DIR = PKG_ROOT / "lib"
 ORACLE_DIR = REPO_ROOT / "oracle"
 
-HIP_SOURCES = ["engine.hip", "score.hip", "forest.hip", "forest_sparse.hip", "shap.hip", "gbdt.hip", "iforest_fit.hip", "ensemble.hip", "ensemble_plan.hip", "blend.hip", "features.hip", "route.hip", "lstm.hip", "mlp.hip", "graph.hip", "text.hip", "abtest.hip", "metrics.hip",
+HIP_SOURCES = ["engine.hip", "score.hip", "forest.hip", "forest_sparse.hip", "shap.hip", "gbdt.hip", "iforest_fit.hip", "ensemble.hip", "ensemble_plan.hip", "blend.hip", "features.hip", "route.hip", "lstm.hip", "mlp.hip", "mlp_fit.hip", "graph.hip", "text.hip", "abtest.hip", "metrics.hip",
                "windows.hip", "snapshot.hip", "ingest.hip", "sink.hip", "model_io.hip", "comm.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-Wno-unused-result", "-Rpass-analysis=kernel-resource-usage"]

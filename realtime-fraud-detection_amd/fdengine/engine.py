@@ -629,6 +629,52 @@ class FraudEngine:
     def mlp_predict_device(self, x_ptr: int, n: int, ld: int, prob_ptr: int) -> None:
         N.call("fd_mlp_predict_device", self._h, C.c_void_p(x_ptr), int(n), int(ld), C.c_void_p(prob_ptr))
 
+    # ------------------------------------------------------------------ training (the MLP member, mlp_fit.hip)
+    def fit_mlp(self, X, y, *, hidden=64, n_layers=3, epochs=20, batch_size=256, optimizer="adam", lr=1e-3,
+                betas=(0.9, 0.999), eps=1e-8, momentum=0.0, weight_decay=0.0, dropout=0.1, pos_weight=1.0, seed=0,
+                init=None):
+        """Fit the MLP member by minibatch training on the engine (fd_mlp_fit_*; the declared semantics are DESIGN
+        §4.16). X: [n, in_dim <= 64] numpy (finite values), or a contiguous f32 torch tensor on this engine's device
+        (then y a uint8 tensor there); y: 0 / 1. The model is in_dim -> hidden x (n_layers - 1) -> 2, started at
+        mlp.random_weights(in_dim, hidden, n_layers, seed) or at init (an MlpWeights: a warm start; its shape then
+        holds and hidden / n_layers are not read). optimizer "adam" (lr, betas, eps, weight_decay) or "sgd" (lr,
+        momentum, weight_decay); dropout after every ReLU; pos_weight the weight of class 1 in the cross-entropy;
+        seed fixes the batches and the masks. -> MlpWeights ready for load_mlp / mlp.save_state_dict, meta["loss_curve"]
+        (one mean batch loss per epoch), meta["steps"] and the parameters under their names."""
+        from . import mlp as M
+        kw = dict(epochs=epochs, batch_size=batch_size, optimizer=optimizer, lr=lr, betas=tuple(betas), eps=eps,
+                  momentum=momentum, weight_decay=weight_decay, dropout=dropout, pos_weight=pos_weight, seed=seed)
+        if type(X).__module__.startswith("torch") and X.is_cuda:
+            import torch
+            if X.dtype != torch.float32 or X.dim() != 2 or not X.is_contiguous():
+                raise ValueError("device input: a contiguous 2-d float32 tensor")
+            y = y.to(device=X.device, dtype=torch.uint8).contiguous()
+            n, ld = X.shape
+            if y.numel() != n:
+                raise ValueError("y: one 0 / 1 label per row of X")
+            init = M._init_for(ld, hidden, n_layers, seed, init)
+            torch.cuda.current_stream(X.device).synchronize()
+            return M.run_fit("fd_mlp_fit_device", (self._h,), C.c_void_p(X.data_ptr()), C.c_void_p(y.data_ptr()), n,
+                             ld, init, kw)
+        X, y = M.fit_xy(X, y)
+        init = M._init_for(X.shape[1], hidden, n_layers, seed, init)
+        return M.run_fit("fd_mlp_fit_host", (self._h,), _ptr(X), _ptr(y), X.shape[0], X.shape[1], init, kw)
+
+    def mlp_grad(self, w, X, y, masks=None, dropout: float = 0.0, pos_weight: float = 1.0):
+        """Loss and gradients of the one batch (X, y) at w under masks, by the step kernel (fd_mlp_grad_host) ->
+        (loss, MlpWeights of gradients); mlp.mlp_grad_ref_host is the host twin."""
+        from . import mlp as M
+        X, y = M.fit_xy(X, y)
+        masks = M.check_masks(masks, w.n_layers, X.shape[0])
+        return M.run_grad("fd_mlp_grad_host", (self._h,), _ptr(X), _ptr(y), _ptr(masks), X.shape[0], X.shape[1], w,
+                          dropout, pos_weight)
+
+    def mlp_fit_batch(self, n: int, epoch: int, step: int, *, n_layers: int = 3, **kw):
+        """What a fit of n rows trains on, from the device (fd_mlp_fit_batch_device) -> (row order, masks);
+        mlp.mlp_fit_batch_host is the host twin."""
+        from . import mlp as M
+        return M.run_batch("fd_mlp_fit_batch_device", (self._h,), n, epoch, step, n_layers, kw)
+
     # ------------------------------------------------------------------ transaction-network features (graph detector)
     def graph_init(self, max_history: int = 10000) -> None:
         """An empty transaction log of the reference's max_history_size (GraphFraudDetector, 2..65536)."""

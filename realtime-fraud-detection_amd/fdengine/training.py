@@ -1,6 +1,6 @@
 """Drop-in for the reference's ModelTrainer (ml/training/model_trainer.py): same constructor, attributes, method names,
-result keys and written paths; both members, XGBoost and IsolationForest, are fitted, saved, reloaded and scored on
-the engine.
+result keys and written paths; the three tabular members — XGBoost, IsolationForest and the PyTorch MLP — are fitted,
+saved, reloaded and scored on the engine.
 
 What differs, on purpose:
 * train_xgboost_model fits with FraudEngine.fit_gbdt (csrc/gbdt.hip) at the reference's parameters (max_depth 6,
@@ -21,6 +21,12 @@ What differs, on purpose:
   scikit-learn and joblib are needed for that file only; IsolationForest.fit never sees the training data.
   auc_score is taken from the engine's raw path-length sums: -decision_function is decreasing in them, so the
   midrank statistic is the reference's.
+* train_graph_neural_model exists: the reference's docstring promises a GNN trainer and holds none, so nothing there
+  writes pytorch/gnn_fraud_model.pth. It fits the registry's architecture (hidden_channels 64, num_layers 3, dropout
+  0.1: an MLP 64 -> 64 -> 64 -> 2) with FraudEngine.fit_mlp (csrc/mlp_fit.hip) on the matrix as the
+  serving side feeds it — padded with zeros to 64 columns and clipped to +-10 (EnsemblePredictor._prepare_features);
+  the trainer's own 33 columns would not load into the 64-wide model — writes a plain state dict with torch.save,
+  reloads it into the engine's MLP slot and scores the held-out split with the serving kernel.
 """
 from __future__ import annotations
 
@@ -38,6 +44,18 @@ from .forest import ForestArrays, load_isolation_forest_joblib, sklearn_iforest_
 ID_COLUMNS = ("is_fraud", "transaction_id", "user_id", "merchant_id")
 XGB_PARAMS = dict(max_depth=6, learning_rate=0.1, subsample=0.8, colsample_bytree=0.8, n_estimators=100)
 IFOREST_PARAMS = dict(n_estimators=100, contamination=0.05)
+MLP_PARAMS = dict(hidden=64, n_layers=3, dropout=0.1)  # the registry's graph_neural hyperparameters
+MLP_WIDTH = 64                                          # the scoring vector's width (_prepare_features)
+
+
+def scoring_matrix(X) -> np.ndarray:
+    """A feature matrix as the serving side hands it to the members: f32, padded with zeros (or cut) to 64 columns,
+    clipped to [-10, 10] (EnsemblePredictor._prepare_features)."""
+    X = np.asarray(X, dtype=np.float64)
+    out = np.zeros((X.shape[0], MLP_WIDTH), np.float32)
+    k = min(X.shape[1], MLP_WIDTH)
+    out[:, :k] = np.clip(X[:, :k], -10.0, 10.0)
+    return out
 
 
 def roc_auc_midrank(y_true, score) -> float:
@@ -99,6 +117,11 @@ class ModelTrainer:
         self.early_stopping_rounds = None
         self.scale_pos_weight = 1.0
         self.evals_result_ = None
+        # the MLP member's fit (FraudEngine.fit_mlp): epochs (default 20), rows per minibatch (default 256) and the
+        # weight of the fraud class in the cross-entropy (default 1.0: unweighted, as the other members' defaults)
+        self.mlp_epochs = 20
+        self.mlp_batch_size = 256
+        self.mlp_pos_weight = 1.0
         self._engine = engine
         self.logger.info(f"Model trainer initialized with output dir: {output_dir}")
 
@@ -262,6 +285,40 @@ class ModelTrainer:
             "training_time_seconds": training_time,
         }
         self.logger.info(f"Isolation Forest training completed in {training_time:.2f}s, AUC: {auc_score:.4f}")
+        return results
+
+    def train_graph_neural_model(self, X_train: np.ndarray, y_train: np.ndarray, X_test: np.ndarray,
+                                 y_test: np.ndarray) -> Dict[str, Any]:
+        """The registry's graph_neural member (model_type "pytorch"), fitted, written, reloaded and scored on the
+        engine; torch only carries the file."""
+        from .mlp import load_mlp_file, save_state_dict
+        self.logger.info("Training graph_neural (MLP) model...")
+        start_time = time.time()
+        eng = self.engine
+        w = eng.fit_mlp(scoring_matrix(X_train), np.asarray(y_train), epochs=self.mlp_epochs,
+                        batch_size=self.mlp_batch_size, pos_weight=self.mlp_pos_weight, seed=self.random_state,
+                        **MLP_PARAMS)
+        model_path = os.path.join(self.output_dir, "pytorch", "gnn_fraud_model.pth")
+        os.makedirs(os.path.dirname(model_path), exist_ok=True)
+        save_state_dict(w, model_path)
+        # score the held-out split with the file just written, as the serving side will (an engine has one MLP slot)
+        if getattr(eng, "mlp_info", None):
+            raise RuntimeError("the engine's MLP slot is in use: train on an engine that serves no MLP")
+        eng.load_mlp(load_mlp_file(model_path))
+        try:
+            y_pred_proba = eng.mlp_predict(scoring_matrix(X_test))
+        finally:
+            eng.unload_mlp()
+        auc_score = roc_auc_midrank(y_test, y_pred_proba)
+        training_time = time.time() - start_time
+        results = {
+            "model_type": "graph_neural",
+            "model_path": model_path,
+            "auc_score": auc_score,
+            "training_time_seconds": training_time,
+            "loss_curve": [float(v) for v in w.meta["loss_curve"]],
+        }
+        self.logger.info(f"graph_neural training completed in {training_time:.2f}s, AUC: {auc_score:.4f}")
         return results
 
     def save_training_metadata(self, results: Dict[str, Any]) -> None:
